@@ -6,13 +6,20 @@ out) over one batch of synthetic ciphertext pairs that is already resident in HB
 Workload: n = 2^15, 4 RNS limbs (the four largest primes < 2^31 that are
 1 mod 2^16), TrivGad hint at the same modulus, B ciphertext pairs per GPU per step.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  `value` = ciphertext pairs all ranks processed / max-over-ranks wall time.
+Rank 0 prints ONE JSON line.  `value` = ciphertext pairs all ranks processed / max-over-ranks wall time,
+`ms_per_step` = that wall time over the K timed steps.
 roofline.achieved = value/n_gpus x 6,291,456 algorithmic bytes per op (read two linear ciphertexts,
 write one, at the reference's 8-byte word) measured with HIP events on the library's stream.
+
+A plain run sets up, warms up, times the K steps and prints the line: nothing else.  --dump-outputs DIR writes a fixed,
+seeded sample of the last timed step's result ciphertexts (dump_outputs).  --full adds, after the timed region, everything
+else the line has carried: the whole-batch check against the oracle's checksums, the extra lines (mul_, Pow basis, general
+index, HomomRLWR pipeline, Tunnel.hs hops, config 2, moduli below 2^30, n = 2^16; each can be skipped with its --no-* option),
+the measured HBM copy bandwidth and PMC traffic next to the roofline, the result all-gather (N > 1) and
 cpu_baseline = the C restatement of Lol's algorithm (oracle/, kind "port"), one thread, rank 0, N = 1 only.
 """
 import argparse
@@ -345,16 +352,36 @@ def config2_line():
     return out
 
 
+DUMP_SAMPLE = 16         # ciphertexts in the --dump-outputs sample: 16 x 2 x 2^15 x 4 words = 32 MiB as float64
+
+
+def dump_outputs(path, out, batch):
+    """--dump-outputs: what the last timed step returned to its caller, as DIR/ct_mul_relin_out.npy -- a fixed, seeded sample
+    of DUMP_SAMPLE result ciphertexts of rank 0's shard, shape (S, 2, n, L) in the host layout of Buf.download, float64 (every
+    residue is below 2^31, so the values are exact) -- and the sampled ciphertext indices as DIR/ct_mul_relin_out_index.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    idx = np.sort(np.random.default_rng(2026).choice(batch, size=min(batch, DUMP_SAMPLE), replace=False))
+    sample = np.stack([out.download(2 * int(ct), 2) for ct in idx]).astype(np.float64)
+    np.save(os.path.join(path, "ct_mul_relin_out.npy"), sample)
+    np.save(os.path.join(path, "ct_mul_relin_out_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=8192, help="ciphertext pairs per GPU per step (weak scaling)")
-    ap.add_argument("--cpu-ops", type=int, default=768, help="ops in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the last timed step's results to DIR/*.npy (float64, 32 MiB)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also check the whole batch against the oracle and run every extra line, "
+                         "measurement and baseline below (a plain run times the headline only)")
+    ap.add_argument("--cpu-ops", type=int, default=768, help="ops in the CPU-baseline sample (0 = skip; with --full)")
     ap.add_argument("--no-pow", dest="pow", action="store_false",
                     help="skip the Pow-basis in/out variant (SURVEY 8d's COEFF line; extra field, after the timed region)")
-    ap.add_argument("--no-full", dest="full", action="store_false",
+    ap.add_argument("--no-full-mul", "--no-full", dest="full_mul", action="store_false",
                     help="skip PT2CT's whole mul_ (modSwitch . keySwitchQuad . modSwitch . (*)), 4 -> 5 -> 3 limbs (extra field)")
     ap.add_argument("--no-general", dest="general", action="store_false",
                     help="skip the general-index line (keySwitchQuadCirc(a*b) on the reference's H5' = F20475 ring)")
@@ -375,6 +402,9 @@ def main():
                     help="launch-structure option for every ring (alch_ring_set_option), e.g. one_stream=1 for kernel traces "
                          "whose durations add up to the step time")
     args = ap.parse_args()
+    if not args.full:            # a plain run: the extra lines and the CPU baseline are --full only
+        args.pow = args.full_mul = args.general = args.pipeline = args.tunnel_hs = args.n16 = args.q30 = args.config2 = False
+        args.cpu_ops = 0
     global RING_OPTS
     RING_OPTS = [(kv.split("=")[0], int(kv.split("=")[1])) for kv in args.opt]
 
@@ -446,12 +476,14 @@ def main():
     wall_max = shard.max_over_ranks(wall, dist, red_dev)
     ev_ms_max = shard.max_over_ranks(ev_ms, dist, red_dev)
     ev_ms_ranks = shard.gather_scalars(ev_ms, dist, red_dev)     # one entry per rank: a straggler is visible
-    checksum = out.checksum(0, 2)
+    if args.dump_outputs and rank == 0:                          # before anything below writes into `out` again
+        dump_outputs(args.dump_outputs, out, B)
+    checksum = out.checksum(0, 2) if args.full else None
     # whole-batch result check on rank 0 (its shard always starts at ciphertext 0, so the seeds are those of the
     # committed fixture): alch_buf_checksum of every result word against the value the C oracle produced offline
     # (tests/golden/batch_checksums.json, generated by tests/golden/make_batch_checksums.py)
     batch_check = None
-    if rank == 0:
+    if rank == 0 and args.full:
         batch_check = check_batch("the headline batch", golden_checksums().get("bench_mul_relin"), B, out.checksum)
 
     # The batch gather (north star: "RCCL over xGMI for the batch gather only"): after timing, every rank
@@ -459,7 +491,7 @@ def main():
     # to the throughput, never inside it: gathering every result would be bound by xGMI ingress (7 x ~153 GB/s per
     # GPU), far below what the ranks produce.
     gather = None
-    if dist is not None:            # any exception here ends the run with a non-zero exit code: no healthy-looking line from a broken RCCL path
+    if dist is not None and args.full:  # any exception here ends the run with a non-zero exit code: no healthy-looking line from a broken RCCL path
         G_CTS = min(B, 256)                               # 256 ciphertexts = 256 MiB of device words per rank
         mine = out.as_torch(0, 2 * G_CTS)
         everyone = torch.empty(world * mine.numel(), dtype=mine.dtype, device=mine.device)
@@ -503,8 +535,8 @@ def main():
         pow_ops = 3 * Bp / (ring.timer_stop() * 1e-3)
         pow_check = check_batch("Pow-basis in/out", golden_checksums().get("bench_extra", {}).get("pow_in_out"), Bp, lambda: out.checksum(0, 2 * Bp))
 
-    full = None
-    if args.full and rank == 0:
+    full_mul = None
+    if args.full_mul and rank == 0:
         # operands on 4 limbs, TrivGad hint one limb longer (KSPNoise, PT2CT.hs:139), result on 3
         from alchemy_amd import capi
         qs_h = [FULL_EXTRA_Q] + CFG3_QS
@@ -524,7 +556,7 @@ def main():
         ops = 3 * Bf / (rh.timer_stop() * 1e-3)
         # compulsory bytes at 8-byte words: two 4-limb linear ciphertexts in, one 3-limb out
         algo = (2 * 2 * 4 + 2 * 3) * (1 << LOGN) * 8
-        full = {"ops_per_s": ops, "workload": "PT2CT mul_: (*) on 4 limbs, modSwitch to the 5-limb hint modulus, "
+        full_mul = {"ops_per_s": ops, "workload": "PT2CT mul_: (*) on 4 limbs, modSwitch to the 5-limb hint modulus, "
                 "keySwitchQuadCirc, modSwitch to 3 limbs; CRT-basis in/out", "moduli_hint": qs_h, "batch": Bf,
                 "algorithmic_bytes_per_op": algo, "achieved_GBs": ops * algo / 1e9,
                 "frac_of_hbm_peak": ops * algo / 1e9 / HBM_PEAK_GBS,
@@ -604,31 +636,11 @@ def main():
         del rr
 
     if rank == 0:
-        copy_bw = hbm_copy_GBs(Ring)
         total_ops = B * world * args.steps
         value = total_ops / wall_max
         # per-GPU achieved algorithmic bandwidth from the HIP-event time of the K launches on the stream
         per_gpu_ops_s = B * args.steps / (ev_ms_max * 1e-3)
         achieved = per_gpu_ops_s * (ALGO_BYTES_PER_OP + HINT_BYTES / B) / 1e9
-        # physical HBM-side bytes per op from the committed PMC passes (profiles/traffic_latest.json: separate
-        # FETCH_SIZE and WRITE_SIZE runs of this script, gfx950 FETCH_SIZE correction applied), turned into
-        # a rate with this run's op rate so that it compares with `achieved`
-        traffic = traffic_per_op = traffic_src = None
-        tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
-        if os.path.exists(tpath):
-            try:
-                tj = json.load(open(tpath))
-                # only a PMC summary taken on these very kernel sources counts; a stale one is reported as null
-                if tj.get("kernel_src_sha16") == kernel_src_sha16():
-                    traffic_per_op = float(tj["hbm_bytes_per_op"])
-                    traffic = per_gpu_ops_s * traffic_per_op / 1e9
-                    traffic_src = {"file": "profiles/traffic_latest.json", "kernel_src_sha16": tj["kernel_src_sha16"],
-                                   "collected": tj.get("collected")}
-                else:
-                    traffic_src = {"file": "profiles/traffic_latest.json", "stale": True,
-                                   "kernel_src_sha16_of_file": tj.get("kernel_src_sha16"), "kernel_src_sha16_now": kernel_src_sha16()}
-            except Exception:
-                traffic = traffic_per_op = None
         line = {
             "metric": "ctxt-mul+relinearize/sec at n=2^15, 4 RNS limbs",
             "value": value, "unit": "ctxt-mul+relin/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -640,47 +652,69 @@ def main():
                        "batch_per_gpu": B, "global_batch": B * world, "sharding": f"dp{world} by ciphertext, no collective in the timed region", "hint": hint_dist,
                        "moduli": CFG3_QS, "device_word_bytes": ring.word_bytes},
             "roofline": {"bound": "hbm", "limiter": "valu", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "hbm_copy_GBs": copy_bw["GBs"], "hbm_copy": copy_bw,
-                         "frac_of_measured_copy": achieved / copy_bw["GBs"],
-                         "frac_at_device_word": per_gpu_ops_s * (DEVICE_WORD_BYTES_PER_OP + HINT_BYTES / 2 / B) / 1e9 / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_bytes_per_op": traffic_per_op, "traffic_source": traffic_src,
-                         "note": "frac prices an op at SURVEY 8d's 6,291,456 B (six ciphertext components at the reference's "
-                                 "8-byte Int64 word); frac_at_device_word prices the same components at the 4-byte word the "
-                                 "device actually moves (3,145,728 B) -- the honest fraction of the 8 TB/s peak for this "
-                                 "build.  bound names the roofline SURVEY 8d prescribes; limiter says what the kernels are "
-                                 "actually bound by (integer VALU issue, DESIGN.md 4).  hbm_copy_GBs = what a plain device-to-device "
-                                 "copy reaches on this very box in this very run (SURVEY 8d asks for it next to the 8 TB/s "
-                                 "specification); frac_of_measured_copy = achieved / that.  traffic = physical GB/s = PMC "
-                                 "(FETCH_SIZE x2 + WRITE_SIZE) bytes per op x this run's ops/s, null when the committed PMC "
-                                 "summary was taken on other kernel sources"},
+                         "frac": achieved / HBM_PEAK_GBS,
+                         "frac_at_device_word": per_gpu_ops_s * (DEVICE_WORD_BYTES_PER_OP + HINT_BYTES / 2 / B) / 1e9 / HBM_PEAK_GBS},
             "hip_event_ms_per_step": ev_ms_max / args.steps,
             "hip_event_ms_per_step_by_rank": [x / args.steps for x in ev_ms_ranks],
-            "batch_checksum": batch_check,
-            "out_checksum": f"{checksum:016x}",
         }
-        if pow_ops is not None:
-            line["pow_basis_in_out_ops_per_s"] = pow_ops
-            line["pow_basis_in_out"] = {"ops_per_s": pow_ops, "batch": min(B, 2048), "batch_checksum": pow_check}
-        if full is not None:
-            line["full_mul"] = full
-        if general is not None:
-            line["general_index"] = general
-        if homomrlwr is not None:
-            line["homomrlwr"] = homomrlwr
-        if tunnel_hs is not None:
-            line["tunnel_hs"] = tunnel_hs
-        if config2 is not None:
-            line["config2"] = config2
-        if q30 is not None:
-            line["moduli_below_2_30"] = q30
-        if n16 is not None:
-            line["n16_six_limbs"] = n16
-        line["result_gather"] = gather
-        if world == 1 and args.cpu_ops > 0:
-            line["cpu_baseline"] = cpu_baseline(args.cpu_ops)
-            line["cpu_baseline_all_cores"] = cpu_baseline_all_cores(max(8, args.cpu_ops // 4))
-        else:
-            line["cpu_baseline"] = None
+        if args.full:
+            copy_bw = hbm_copy_GBs(Ring)
+            # physical HBM-side bytes per op from the committed PMC passes (profiles/traffic_latest.json: separate
+            # FETCH_SIZE and WRITE_SIZE runs of this script, gfx950 FETCH_SIZE correction applied), turned into
+            # a rate with this run's op rate so that it compares with `achieved`
+            traffic = traffic_per_op = traffic_src = None
+            tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
+            if os.path.exists(tpath):
+                try:
+                    tj = json.load(open(tpath))
+                    # only a PMC summary taken on these very kernel sources counts; a stale one is reported as null
+                    if tj.get("kernel_src_sha16") == kernel_src_sha16():
+                        traffic_per_op = float(tj["hbm_bytes_per_op"])
+                        traffic = per_gpu_ops_s * traffic_per_op / 1e9
+                        traffic_src = {"file": "profiles/traffic_latest.json", "kernel_src_sha16": tj["kernel_src_sha16"],
+                                       "collected": tj.get("collected")}
+                    else:
+                        traffic_src = {"file": "profiles/traffic_latest.json", "stale": True,
+                                       "kernel_src_sha16_of_file": tj.get("kernel_src_sha16"), "kernel_src_sha16_now": kernel_src_sha16()}
+                except Exception:
+                    traffic = traffic_per_op = None
+            line["roofline"].update({
+                "hbm_copy_GBs": copy_bw["GBs"], "hbm_copy": copy_bw, "frac_of_measured_copy": achieved / copy_bw["GBs"],
+                "traffic": traffic, "traffic_bytes_per_op": traffic_per_op, "traffic_source": traffic_src,
+                "note": "frac prices an op at SURVEY 8d's 6,291,456 B (six ciphertext components at the reference's "
+                        "8-byte Int64 word); frac_at_device_word prices the same components at the 4-byte word the "
+                        "device actually moves (3,145,728 B) -- the honest fraction of the 8 TB/s peak for this "
+                        "build.  bound names the roofline SURVEY 8d prescribes; limiter says what the kernels are "
+                        "actually bound by (integer VALU issue, DESIGN.md 4).  hbm_copy_GBs = what a plain device-to-device "
+                        "copy reaches on this very box in this very run (SURVEY 8d asks for it next to the 8 TB/s "
+                        "specification); frac_of_measured_copy = achieved / that.  traffic = physical GB/s = PMC "
+                        "(FETCH_SIZE x2 + WRITE_SIZE) bytes per op x this run's ops/s, null when the committed PMC "
+                        "summary was taken on other kernel sources"})
+            line["batch_checksum"] = batch_check
+            line["out_checksum"] = f"{checksum:016x}"
+            if pow_ops is not None:
+                line["pow_basis_in_out_ops_per_s"] = pow_ops
+                line["pow_basis_in_out"] = {"ops_per_s": pow_ops, "batch": min(B, 2048), "batch_checksum": pow_check}
+            if full_mul is not None:
+                line["full_mul"] = full_mul
+            if general is not None:
+                line["general_index"] = general
+            if homomrlwr is not None:
+                line["homomrlwr"] = homomrlwr
+            if tunnel_hs is not None:
+                line["tunnel_hs"] = tunnel_hs
+            if config2 is not None:
+                line["config2"] = config2
+            if q30 is not None:
+                line["moduli_below_2_30"] = q30
+            if n16 is not None:
+                line["n16_six_limbs"] = n16
+            line["result_gather"] = gather
+            if world == 1 and args.cpu_ops > 0:
+                line["cpu_baseline"] = cpu_baseline(args.cpu_ops)
+                line["cpu_baseline_all_cores"] = cpu_baseline_all_cores(max(8, args.cpu_ops // 4))
+            else:
+                line["cpu_baseline"] = None
         print(json.dumps(line), flush=True)
 
     if dist is not None:

@@ -25,7 +25,7 @@ def _run(extra_env):
     env = dict(os.environ, ALCH_DIST_BACKEND="gloo", ALCH_FORCE_DEVICE="0", **extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "64", "--cpu-ops", "0", "--no-full", "--no-pow", "--no-general", "--pipeline-batch", "48"]
+           "--batch", "64", "--full", "--cpu-ops", "0", "--no-full-mul", "--no-pow", "--no-general", "--pipeline-batch", "48"]
     return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
 
 
@@ -59,8 +59,8 @@ def test_one_rank_process_group_runs_every_collective_through_rccl():
     env = dict(os.environ, ALCH_DIST_FORCE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", LOCAL_RANK="0",
                WORLD_SIZE="1")
     env.pop("ALCH_DIST_BACKEND", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64", "--cpu-ops", "0",
-           "--no-full", "--no-pow", "--no-general", "--no-tunnel-hs", "--no-config2", "--no-q30", "--pipeline-batch", "16"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64", "--full", "--cpu-ops", "0",
+           "--no-full-mul", "--no-pow", "--no-general", "--no-tunnel-hs", "--no-config2", "--no-q30", "--pipeline-batch", "16"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 A=$1; B=$2; R=${3:-2}
 run() {
     lib=$1; [ "$lib" = product ] && lib=alchemy_amd/lib/libalchemy_hip.so
-    ALCH_LIB_PATH=$lib timeout -k 10 300 python3 bench.py --steps 10 --warmup 2 --cpu-ops 0 --no-general --no-pipeline --no-tunnel-hs --no-config2 2>/dev/null | python3 -c "
+    ALCH_LIB_PATH=$lib timeout -k 10 300 python3 bench.py --steps 10 --warmup 2 --full --cpu-ops 0 --no-general --no-pipeline --no-tunnel-hs --no-config2 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

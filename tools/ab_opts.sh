@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 for o in "$@"; do
     args=""
     for kv in $o; do args="$args --opt $kv"; done
-    timeout -k 10 200 python3 bench.py --no-config2 --no-q30 --no-n16 --no-tunnel-hs --no-general --no-pipeline --cpu-ops 0 --steps 4 $args 2>/dev/null | python3 -c "
+    timeout -k 10 200 python3 bench.py --full --no-config2 --no-q30 --no-n16 --no-tunnel-hs --no-general --no-pipeline --cpu-ops 0 --steps 4 $args 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -2,7 +2,7 @@
 # AB_FLAGS="" adds the full mul_ and Pow-basis lines to every run (columns 3 and 4).
 # Same-box comparison of library variants (tools/build_variant.sh) on the headline: tools/ab_variants.sh nt_in nt_out ...   ("cur" = current build)
 mkdir -p gpurun_out; out=gpurun_out/ab_variants.txt; : > $out
-F="${AB_FLAGS:---no-pow --no-full} --no-general --no-pipeline --no-tunnel-hs --no-config2 --no-q30 --no-n16 --cpu-ops 0 --steps 10 --warmup 2"
+F="--full ${AB_FLAGS:---no-pow --no-full-mul} --no-general --no-pipeline --no-tunnel-hs --no-config2 --no-q30 --no-n16 --cpu-ops 0 --steps 10 --warmup 2"
 for round in 1 2; do
 for v in cur "$@"; do
   lib=""; [ "$v" != cur ] && lib=alchemy_amd/lib/variants/$v.so

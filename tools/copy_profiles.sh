@@ -1,5 +1,5 @@
 #!/bin/bash
-# Run HERE after tools/profile_round.sh TAG, tools/pmc_valu.sh TAG and a bench.py run into gpurun_out/TAG_bench_final.json on the GPU
+# Run after tools/profile_round.sh TAG, tools/pmc_valu.sh TAG and a `bench.py --full` run saved as TAG_bench_final.json on the GPU
 # box: copies the summaries the judge reads from gpurun_out/ (scratch) into profiles/ (tracked).   usage: tools/copy_profiles.sh r04
 set -e
 tag=${1:-r04}

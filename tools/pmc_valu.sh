@@ -18,7 +18,7 @@ run() { name=$1; shift; echo "== $name: rocprofv3 --kernel-trace --pmc $CTRS -- 
         timeout -k 10 400 rocprofv3 --kernel-trace --pmc $CTRS --output-format csv -d "$out" -o "$name" -- "$@" > "$out/$name.log" 2>&1 || echo "$name failed" >> "$out/commands.txt"; }
 run headline  python3 $root/bench.py --steps 1 --warmup 0 --batch 2048 --cpu-ops 0 --no-full --no-pow --no-general --no-pipeline --no-tunnel-hs --no-config2 --no-q30 --no-n16 --opt one_stream=1
 # round 4: PT2CT's whole mul_ (k_ks_accum_half<UP>, k_rescale_out_lin) and the Tunnel.hs hops (k_gen_crt_base2_digits, k_tunnel_mac_e)
-run full_mul  python3 $root/bench.py --steps 1 --warmup 0 --batch 2048 --cpu-ops 0 --no-pow --no-general --no-pipeline --no-tunnel-hs --no-config2 --no-q30 --no-n16 --opt one_stream=1
+run full_mul  python3 $root/bench.py --steps 1 --warmup 0 --batch 2048 --full --cpu-ops 0 --no-pow --no-general --no-pipeline --no-tunnel-hs --no-config2 --no-q30 --no-n16 --opt one_stream=1
 run tunnel_hs python3 $root/tools/bench_tunnel.py 1024
 run general   python3 $root/tools/bench_general.py 20475
 run homomrlwr python3 $root/tools/bench_homomrlwr.py 1024
