@@ -82,7 +82,7 @@ struct alch_ring {
     size_t chunk = 1024;                       // ciphertexts per (tensor_intt, ks_accum) launch pair
     void* ws_full = nullptr;                   // ct_mul_full scratch: per pipeline digits + key-switched chunk + stash
     size_t ws_full_bytes = 0;
-    hipEvent_t ev_x = nullptr;                 // cross-ring ordering (ct_mul_full)
+    hipEvent_t ev_x = nullptr;                 // cross-ring ordering (ext_order)
     int device = 0;                            // HIP device the ring's streams, tables and buffers live on
     LaunchOpts opts;                           // launch-structure options (alch_ring_set_option)
     bool one_stream = false;
@@ -1387,7 +1387,10 @@ extern "C" int alch_timer_stop(alch_ring* r, float* ms) try {
 // ------------------------------------------------------------------------------------------------------
 // helpers
 // ------------------------------------------------------------------------------------------------------
-static inline bool split_ring_fwd(const alch_ring* r) { return !r->gen && r->logn > (r->word == 4 ? 15 : 14); }   // == split_ring()
+// rings whose limb-polynomial does not fit one LDS-resident transform (k_crt_split); a general-index ring has logn = 0
+static inline bool split_ring(const alch_ring* r) { return r->logn > (r->word == 4 ? 15 : 14); }
+// f<W>(args) for the ring's word size
+#define ALCH_BY_WORD(ringp, f, ...) ((ringp)->word == 4 ? f<u32>(__VA_ARGS__) : f<u64>(__VA_ARGS__))
 static inline size_t elem_words(const alch_ring* r) { return (size_t)r->L * r->n; }
 static inline size_t elem_bytes(const alch_ring* r) { return elem_words(r) * (size_t)r->word; }
 
@@ -1415,6 +1418,17 @@ static hipError_t dispatch(int logn, const NttCall<u64>& c) {
     if (logn <= 14) return dispatch64_big(logn, c);
     return dispatch64_15(logn, c);
 }
+// Queue one transform-engine / pass-engine launch: ALCH_OK, or ALCH_E_HIP with "<what> launch: <HIP's text>".
+template <typename W>
+static int launch(const alch_ring* r, const NttCall<W>& c, const char* what) {
+    const hipError_t e = dispatch(r->logn, c);
+    return e == hipSuccess ? ALCH_OK : fail(ALCH_E_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+}
+template <typename W>
+static int launch(const GenCall<W>& g, const char* what) {
+    const hipError_t e = gen_dispatch(g);
+    return e == hipSuccess ? ALCH_OK : fail(ALCH_E_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+}
 
 template <typename W>
 static int do_crt(alch_ring* r, void* data, size_t first_elem, size_t count, bool inverse, const void* src = nullptr,
@@ -1435,8 +1449,7 @@ static int do_crt(alch_ring* r, void* data, size_t first_elem, size_t count, boo
             const size_t now = std::min<size_t>(polys - done, (size_t)1 << 30);
             g.first_poly = first_elem * (size_t)r->L + done;
             g.npoly = now;
-            hipError_t e = gen_dispatch(g);
-            if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("general-index crt launch: ") + hipGetErrorString(e));
+            if (int rc = launch(g, "general-index crt")) return rc;
             done += now;
         }
         return ALCH_OK;
@@ -1454,8 +1467,7 @@ static int do_crt(alch_ring* r, void* data, size_t first_elem, size_t count, boo
         size_t now = std::min<size_t>(polys - done, (size_t)1 << 30);
         c.first_poly = first_elem * (size_t)r->L + done;
         c.npoly = now;
-        hipError_t e = dispatch(r->logn, c);
-        if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("crt launch: ") + hipGetErrorString(e));
+        if (int rc = launch(r, c, "crt")) return rc;
         done += now;
     }
     return ALCH_OK;
@@ -1466,7 +1478,7 @@ static int buf_crt(alch_buf* b, size_t first, size_t count, bool inverse) {
     if (!range_ok(first, count, b->n_elems)) return fail(ALCH_E_INVALID, "element range out of bounds");
     alch_ring* r = b->ring;
     BIND(r);
-    return r->word == 4 ? do_crt<u32>(r, b->dptr, first, count, inverse) : do_crt<u64>(r, b->dptr, first, count, inverse);
+    return ALCH_BY_WORD(r, do_crt, r, b->dptr, first, count, inverse);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1622,7 +1634,7 @@ static int transfer(alch_ring* r, void* dev_base, size_t first, size_t count, in
         const size_t now = std::min(per, count - done);
         char* dev = reinterpret_cast<char*>(dev_base) + (first + done) * elem_bytes(r);
         int64_t* h = host + done * elem_words(r);
-        int rc = r->word == 4 ? do_transfer<u32>(r, dev, now, h, to_device) : do_transfer<u64>(r, dev, now, h, to_device);
+        int rc = ALCH_BY_WORD(r, do_transfer, r, dev, now, h, to_device);
         if (rc != ALCH_OK) return rc;
         done += now;
     }
@@ -1789,7 +1801,7 @@ extern "C" int alch_scale(alch_ring* r, int64_t* a, const uint64_t* s) try {
     int rc = scratch_get(r, 1, &t.b);
     if (rc != ALCH_OK) return rc;
     if ((rc = alch_buf_upload(t.b, 0, 1, a)) != ALCH_OK) return rc;
-    rc = r->word == 4 ? do_scale<u32>(r, t.b->dptr, t.b->dptr, 1, s) : do_scale<u64>(r, t.b->dptr, t.b->dptr, 1, s);
+    rc = ALCH_BY_WORD(r, do_scale, r, t.b->dptr, t.b->dptr, 1, s);
     if (rc != ALCH_OK) return rc;
     return alch_buf_download(t.b, 0, 1, a);
 } catch (...) { return abi_catch(); }
@@ -1907,7 +1919,7 @@ extern "C" int alch_buf_scale(alch_buf* dst, const alch_buf* src, size_t count, 
     if (count > dst->n_elems || count > src->n_elems) return fail(ALCH_E_INVALID, "count out of bounds");
     alch_ring* r = dst->ring;
     BIND(r);
-    return r->word == 4 ? do_scale<u32>(r, dst->dptr, src->dptr, count, s) : do_scale<u64>(r, dst->dptr, src->dptr, count, s);
+    return ALCH_BY_WORD(r, do_scale, r, dst->dptr, src->dptr, count, s);
 } catch (...) { return abi_catch(); }
 
 extern "C" int alch_buf_decompose_triv(const alch_buf* src, size_t src_index, alch_buf* dst, size_t dst_first) try {
@@ -2001,8 +2013,7 @@ static int do_columns(alch_ring* r, GenOp op, void* data, size_t first, size_t c
         const size_t now = std::min<size_t>(count - done, ((size_t)1 << 30) / (size_t)r->L);
         g.first_poly = first + done * stride;
         g.npoly = now * (size_t)r->L;
-        hipError_t e = gen_dispatch(g);
-        if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("general-index column launch: ") + hipGetErrorString(e));
+        if (int rc = launch(g, "general-index column")) return rc;
         done += now;
     }
     return ALCH_OK;
@@ -2010,8 +2021,7 @@ static int do_columns(alch_ring* r, GenOp op, void* data, size_t first, size_t c
 
 static int columns(alch_ring* r, GenOp op, void* data, size_t first, size_t count, size_t stride, hipStream_t stream = nullptr,
                    const void* src = nullptr) {
-    return r->word == 4 ? do_columns<u32>(r, op, data, first, count, stride, stream, src)
-                        : do_columns<u64>(r, op, data, first, count, stride, stream, src);
+    return ALCH_BY_WORD(r, do_columns, r, op, data, first, count, stride, stream, src);
 }
 
 // mulG (divide = false) or divG on elements [first, first + count) of a buffer, basis ALCH_BASIS_*.
@@ -2118,11 +2128,11 @@ extern "C" int alch_buf_tensor_op(alch_buf* dst, size_t dst_first, const alch_bu
     int rc;
     if (op == ALCH_T_CRT || op == ALCH_T_CRTINV) {
         const bool inv = op == ALCH_T_CRTINV;
-        if (in_place || split_ring_fwd(r)) {                       // the split transforms (n = 2^16 / 64-bit 2^15) work in place only
+        if (in_place || split_ring(r)) {                       // the split transforms (n = 2^16 / 64-bit 2^15) work in place only
             if ((rc = copy_first()) != ALCH_OK) return rc;
-            return r->word == 4 ? do_crt<u32>(r, d, 0, count, inv) : do_crt<u64>(r, d, 0, count, inv);
+            return ALCH_BY_WORD(r, do_crt, r, d, 0, count, inv);
         }
-        return r->word == 4 ? do_crt<u32>(r, d, 0, count, inv, f) : do_crt<u64>(r, d, 0, count, inv, f);
+        return ALCH_BY_WORD(r, do_crt, r, d, 0, count, inv, f);
     }
     const bool trivial = !r->gen || r->gh.rad == 1;                   // two-power index: g = 1, L = identity
     if (trivial) return copy_first();
@@ -2182,31 +2192,72 @@ extern "C" int alch_buf_add_public(alch_buf* cts, const alch_buf* pub, size_t pu
 // ------------------------------------------------------------------------------------------------------
 // the hot path
 // ------------------------------------------------------------------------------------------------------
-// rings whose limb-polynomial does not fit one LDS-resident transform (k_crt_split)
-static bool split_ring(const alch_ring* r) { return r->logn > (r->word == 4 ? 15 : 14); }
+// order work's stream after everything queued on other's stream (before), or hand back: other's stream after work's (!before)
+static int ext_order(alch_ring* work, alch_ring* other, bool before) {
+    if (work->stream == other->stream) return ALCH_OK;
+    if (!work->ev_x) HIP_TRY(hipEventCreateWithFlags(&work->ev_x, hipEventDisableTiming));
+    if (before) { HIP_TRY(hipEventRecord(work->ev_x, other->stream)); HIP_TRY(hipStreamWaitEvent(work->stream, work->ev_x, 0)); }
+    else { HIP_TRY(hipEventRecord(work->ev_x, work->stream)); HIP_TRY(hipStreamWaitEvent(other->stream, work->ev_x, 0)); }
+    return ALCH_OK;
+}
 
-// keySwitchQuadCirc hint (a * b), unfused: element-wise tensor product, batched crtInv of c2, decompose, batched crt
-// of the digits, hint inner product.  Serves
-//   * BaseBGad 2 hints (PT2CT.hs:140; Tunnel.hs:24 / HomomRLWR.hs:46 pick that gadget): D = sum_i ceil(log2 q_i)
-//     digits, each reduced into every limb and transformed -- D*L crt per ciphertext against L*(L-1) for TrivGad,
-//     two orders of magnitude heavier by construction;
-//   * TrivGad on rings too large for one LDS-resident transform (n = 2^16 / 2^15), where the fused kernels do
-//     not exist and crt runs as k_crt_split.
+// CRT image of g in Montgomery form, per limb (SymmSHE's (*) applies mulG); all-null where g = 1 (two-power index, radical 1)
+template <typename W>
+static GTab<W> g_table(alch_ring* r) {
+    GTab<W> gt{};
+    if (r->gen && r->gh.rad > 1) for (int j = 0; j < r->L; ++j) gt.p[j] = gen_dev<W>(r).gcrt[j];
+    return gt;
+}
+
+// modSwitch up folded into a scalar: s times the `dup` leading moduli of r that the switch adds (inverse: divided by them), mod q_j
+static u64 up_scalar(const alch_ring* r, int dup, int j, u64 s, bool inverse = false) {
+    const u64 qj = r->q[j];
+    u64 v = s % qj;
+    for (int u = 0; u < dup; ++u) v = h_mulmod(v, inverse ? h_invmod(r->q[u] % qj, qj) : r->q[u] % qj, qj);
+    return v;
+}
+
+// q_u^-1 mod q_(u+j) in Montgomery form, j = 1 .. L - u - 1: k_rescale_drop0's constants on the suffix ring that starts at limb u
+template <typename W>
+static Scal<W> drop0_inv_mont(const alch_ring* r, int u) {
+    Scal<W> sm;
+    for (int j = 0; j < MAXL; ++j) sm.v[j] = 0;
+    for (int j = 1; u + j < r->L; ++j) {
+        const u64 qj = r->q[u + j];
+        sm.v[j] = (W)h_mulmod(h_powmod(r->q[u] % qj, qj - 2, qj), h_powmod(2, 8 * (u64)sizeof(W), qj), qj);
+    }
+    return sm;
+}
+
+// DevRing of the suffix ring that starts at limb u of r (device tables shared with the ring itself)
+template <typename W>
+static DevRing<W> suffix_view(const alch_ring* r, int u) {
+    DevRing<W> d = dev_ring<W>(r);
+    d.L = r->L - u;
+    for (int j = 0; j + u < r->L; ++j) {
+        d.mod[j] = d.mod[j + u]; d.ninv_m[j] = d.ninv_m[j + u]; d.w1ninv_m[j] = d.w1ninv_m[j + u];
+        d.twf[j] = d.twf[j + u]; d.twi[j] = d.twi[j + u]; d.twp[j] = d.twp[j + u];
+        d.tws[j] = d.tws[j + u]; d.twsi[j] = d.twsi[j + u];
+    }
+    return d;
+}
+
+// View of the last L - u limbs of a general-index ring (device tables shared with the ring itself).
+template <typename W>
+static void gen_suffix_view(alch_ring* r, int u, DevRing<W>& d, GenDev<W>& g) {
+    d = dev_ring<W>(r);
+    g = gen_dev<W>(r);
+    d.L = r->L - u;
+    for (int j = 0; j + u < r->L; ++j) {
+        d.mod[j] = d.mod[j + u];
+        g.tabf[j] = g.tabf[j + u]; g.tabi[j] = g.tabi[j + u]; g.iscale_m[j] = g.iscale_m[j + u];
+        g.gcrt[j] = g.gcrt[j + u]; g.gcrt_inv[j] = g.gcrt_inv[j + u]; g.radinv_m[j] = g.radinv_m[j + u];
+    }
+}
+
 // The fused general-index key switch (k_gen_tensor_inv + k_gen_ks, kernel_gen.hpp): TrivGad, 32-bit words, n <= 12288.
 static bool gen_ks_fused(const alch_ring* r, const alch_hint* hint) {
     return r->gen && r->word == 4 && hint->gadget == ALCH_GAD_TRIV && r->n <= (u32)(GEN_KS_T * GEN_KS_NPT) && r->opts.gen_fused;
-}
-
-// keySwitchQuadCirc hint (a * b) for `now` ciphertexts through the two fused general-index kernels; a, b live on the last
-// L - dup limbs of r's moduli (Ls limbs, ring_in), ks receives [now][2][L][n].
-static int launch_gen_ks(alch_ring* r, const alch_hint* hint, const u32* a, const u32* b, u32* ks, u32* c2pow, size_t now, int dup,
-                         const Scal<u32>& sr2, hipStream_t stream) {
-    GenKsArgs<u32> A{};
-    A.a = a; A.b = b; A.c2pow = c2pow; A.hint = reinterpret_cast<const u32*>(hint->dptr); A.out = ks;
-    A.sr2 = sr2; A.dup = dup; A.balanced = r->balanced ? 1 : 0; A.use_g = r->gh.rad > 1 ? 1 : 0;
-    hipError_t e = gen_ks_dispatch(r->d32, r->g32, A, now, stream);
-    if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("general-index fused key switch launch: ") + hipGetErrorString(e));
-    return ALCH_OK;
 }
 
 template <typename W>
@@ -2224,123 +2275,154 @@ static void launch_hint_mac(alch_ring* r, hipStream_t stream, W* out, const W* d
     }
 }
 
+// ---- the composed key switch: keySwitchQuadCirc hint (a * b) from the element-wise kernels and batched transforms -------------
+// Element-wise tensor product, batched crtInv of c2, decompose, batched crt of the digits, hint inner product.  Serves
+//   * BaseBGad 2 hints (PT2CT.hs:140; Tunnel.hs:24 / HomomRLWR.hs:46 pick that gadget): D = sum_i ceil(log2 q_i)
+//     digits, each reduced into every limb and transformed -- D*L crt per ciphertext against L*(L-1) for TrivGad,
+//     two orders of magnitude heavier by construction;
+//   * TrivGad on rings too large for one LDS-resident transform (n = 2^16 / 2^15), where the fused kernels do
+//     not exist and crt runs as k_crt_split;
+//   * TrivGad on general-index rings.
+// KsStage holds what every chunk of one call shares: which digit kernel serves (the only copy of that ladder's predicates), the
+// scratch a ciphertext needs under them, and the operands that do not move with the chunk.
 template <typename W>
-static int do_mul_relin_unfused(alch_ring* r, const alch_hint* hint, const void* a, const void* b, void* out, size_t batch,
-                                const uint64_t* s_pre) {
-    Scal<u32> first, kd;
-    const bool base2 = hint->gadget == ALCH_GAD_BASE2;
-    const u32 D = base2 ? (u32)base2_layout(r, first, kd) : (u32)r->L;
+struct KsStage {
+    const alch_hint* hint;
+    int dup;                    // leading limbs of r the operands lack: the modSwitch up of alch_ct_mul_full, folded in
+    bool have_c2;               // c2 arrives on the powerful basis of r: no tensor product, no c2 scratch
+    bool base2;
+    bool fused_digits;          // TrivGad: decompose + reduce in the digit transforms' loader; the diagonal digits are c2's CRT copy
+    bool gen_fused;             // k_gen_tensor_inv + k_gen_ks
+    bool no_digits;             // the one-kernel forms (k_ks_accum_split, k_gen_ks) keep no digits in HBM: only c2 in both bases
+    bool compact;               // general index below the hint's ring: the limbs the first modSwitch adds are zero in c2, so c2, its crtInv and
+                                // its digits are kept on the operands' L - dup limbs only (a fifth to a half of the digit transforms of PT2CT's products)
+    u32 D;                      // gadget digits per ciphertext
+    Scal<u32> first, kd;        // BaseBGad 2 layout
+    size_t elems;               // scratch per ciphertext, in ring elements: c2 in both bases (unless it arrives ready) + digits (unless no_digits)
+    Scal<W> sr2;                // the tensor product's scalar (times R^2)
+    GTab<W> gt;
+    char* scratch;              // c2 | c2crt | dig, each for `chunk` ciphertexts (a ready c2: dig only)
+    size_t chunk;
+};
+
+template <typename W>
+static KsStage<W> ks_stage_plan(alch_ring* r, const alch_hint* hint, int dup, bool have_c2) {
+    KsStage<W> s{};
+    s.hint = hint; s.dup = dup; s.have_c2 = have_c2;
+    s.base2 = hint->gadget == ALCH_GAD_BASE2;
+    s.D = s.base2 ? (u32)base2_layout(r, s.first, s.kd) : (u32)r->L;
+    s.fused_digits = !s.base2 && (split_ring(r) || r->gen);
+    s.gen_fused = !have_c2 && gen_ks_fused(r, hint);
+    s.no_digits = s.fused_digits && ((!r->gen && r->opts.split_fused) || s.gen_fused);
+    s.compact = r->gen && dup > 0;
+    s.elems = (have_c2 ? 0 : 2) + (s.no_digits ? 0 : s.D);
+    if (!have_c2) s.gt = g_table<W>(r);
+    return s;
+}
+
+// The stage for `now` <= s.chunk ciphertexts: out [now][2][L][n] = (c0, c1) of a * b + switch(hint, c2).  a, b: the operands on the last
+// L - s.dup limbs of r; or, for s.have_c2, c2pow: `now` elements of r, and out already holds (c0, c1).
+template <typename W>
+static int ks_stage(alch_ring* r, const KsStage<W>& s, const W* a, const W* b, const W* c2pow, W* out, size_t now) {
     const size_t eb = elem_bytes(r);
-    // scratch: c2 (1 element) + digits (D elements) per ciphertext of a chunk, at most ~1 GiB
-    const bool fused_digits = !base2 && (split_ring(r) || r->gen);
-    // the one-kernel forms (k_ks_accum_split, k_gen_ks) keep no digits in HBM: only c2 in both bases
-    const bool no_digits = fused_digits && ((!r->gen && r->opts.split_fused) || gen_ks_fused(r, hint));
-    const size_t per_ct = (no_digits ? 2 : D + 2) * eb;
-    size_t chunk = std::max<size_t>(1, (r->scratch_mib << 20) / per_ct);
-    chunk = std::min(chunk, batch);
-    int rc = ensure_ws(&r->ws_digits, &r->ws_digits_bytes, chunk * per_ct);
-    if (rc != ALCH_OK) return rc;
-    char* c2 = reinterpret_cast<char*>(r->ws_digits);
-    char* c2crt = c2 + chunk * eb;                       // CRT-basis copy of c2 (diagonal digits, split rings)
-    char* dig = c2crt + chunk * eb;
-    Scal<W> sr2;
-    scal_to_mont<W>(r, s_pre, 2, sr2);
-    GTab<W> gt{};
-    if (r->gen) for (int j = 0; j < r->L; ++j) gt.p[j] = r->gh.rad > 1 ? gen_dev<W>(r).gcrt[j] : nullptr;
-    const size_t ct_bytes = 2 * eb;
-    for (size_t done = 0; done < batch; done += chunk) {
-        const size_t now = std::min(chunk, batch - done);
-        const W* pa = reinterpret_cast<const W*>(reinterpret_cast<const char*>(a) + done * ct_bytes);
-        const W* pb = reinterpret_cast<const W*>(reinterpret_cast<const char*>(b) + done * ct_bytes);
-        W* po = reinterpret_cast<W*>(reinterpret_cast<char*>(out) + done * ct_bytes);
-        const size_t words = now * elem_words(r);
+    const int L = r->L, Ls = L - s.dup;
+    const W* hint = reinterpret_cast<const W*>(s.hint->dptr);
+    char* c2crt = s.scratch + s.chunk * eb;                       // CRT-basis copy of c2 (diagonal digits, split rings)
+    W* dig = reinterpret_cast<W*>(s.have_c2 ? s.scratch : c2crt + s.chunk * eb);
+    W* diag = s.fused_digits ? reinterpret_cast<W*>(c2crt) : nullptr;
+    NttCall<W> nc{};
+    nc.ring = &dev_ring<W>(r); nc.stream = r->stream; nc.balanced = r->balanced;
+    GenCall<W> gc{};
+    gc.ring = &dev_ring<W>(r); gc.gen = &gen_dev<W>(r); gc.stream = r->stream; gc.balanced = r->balanced;
+    int rc;
+    if (!s.have_c2) {
+        W* c2 = reinterpret_cast<W*>(s.scratch);
         if constexpr (sizeof(W) == 4) {
-            if (gen_ks_fused(r, hint)) {                          // two fused launches: tensor + crtInv, digit transforms + hint products
-                if ((rc = launch_gen_ks(r, hint, pa, pb, po, reinterpret_cast<u32*>(c2), now, 0, sr2, r->stream)) != ALCH_OK) return rc;
-                continue;
+            if (s.gen_fused) {                                    // two fused launches: tensor + crtInv, digit transforms + hint products
+                GenKsArgs<u32> A{};
+                A.a = a; A.b = b; A.c2pow = c2; A.hint = hint; A.out = out;
+                A.sr2 = s.sr2; A.dup = s.dup; A.balanced = r->balanced ? 1 : 0; A.use_g = r->gh.rad > 1 ? 1 : 0;
+                const hipError_t e = gen_ks_dispatch(r->d32, r->g32, A, now, r->stream);
+                return e == hipSuccess ? ALCH_OK : fail(ALCH_E_HIP, std::string("general-index fused key switch launch: ") + hipGetErrorString(e));
             }
         }
-        ALCH_LAUNCH_VW(k_tensor_ew, r, words, r->stream, dev_ring<W>(r), pa, pb, po,
-                           (W*)c2, now, sr2, 0, fused_digits ? (W*)c2crt : (W*)nullptr, gt);
+        // (*) and modSwitch up
+        ALCH_LAUNCH_VW(k_tensor_ew, r, now * elem_words(r), r->stream, dev_ring<W>(r), a, b, out, c2, now, s.sr2, s.dup,
+                       diag, s.gt, s.compact ? 1 : 0);
         HIP_TRY(hipGetLastError());
-        if ((rc = do_crt<W>(r, c2, 0, now, true)) != ALCH_OK) return rc;
-        if (fused_digits && r->gen) {                               // general index: the same, on the pass engine
+        if (s.compact) {
+            DevRing<W> dv; GenDev<W> gv;
+            gen_suffix_view<W>(r, s.dup, dv, gv);
             GenCall<W> g{};
-            g.op = GEN_CRT_DIGITS;
-            g.ring = &dev_ring<W>(r);
-            g.gen = &gen_dev<W>(r);
-            g.stream = r->stream;
-            g.src = reinterpret_cast<const W*>(c2);
-            g.data = reinterpret_cast<W*>(dig);
-            g.npoly = now * (size_t)r->L * (size_t)r->L;
-            g.balanced = r->balanced;
-            hipError_t e = gen_dispatch(g);
-            if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("general-index crt_digits launch: ") + hipGetErrorString(e));
-            launch_hint_mac<W>(r, r->stream, po, (const W*)dig, (const W*)hint->dptr, now, D, (const W*)c2crt);
-            HIP_TRY(hipGetLastError());
-            continue;
-        }
-        if (fused_digits && r->opts.split_fused) {                  // split rings: digit transforms + hint products in one kernel
-            NttCall<W> dc{};
-            dc.op = OP_KS_SPLIT;
-            dc.ring = &dev_ring<W>(r);
-            dc.stream = r->stream;
-            dc.src = reinterpret_cast<const W*>(c2);
-            dc.a = reinterpret_cast<const W*>(c2crt);
-            dc.hint = reinterpret_cast<const W*>(hint->dptr);
-            dc.out = po;
-            dc.nct = now;
-            dc.dup = 0;
-            dc.balanced = r->balanced;
-            hipError_t e = dispatch(r->logn, dc);
-            if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("ks_accum_split launch: ") + hipGetErrorString(e));
-            continue;
-        }
-        if (fused_digits) {                                         // decompose fused into the digit transforms
-            NttCall<W> dc{};
-            dc.op = OP_CRT_DIGITS;
-            dc.ring = &dev_ring<W>(r);
-            dc.stream = r->stream;
-            dc.src = reinterpret_cast<const W*>(c2);
-            dc.data = reinterpret_cast<W*>(dig);
-            dc.npoly = now * (size_t)r->L * (size_t)r->L;
-            dc.balanced = r->balanced;
-            hipError_t e = dispatch(r->logn, dc);
-            if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("crt_digits launch: ") + hipGetErrorString(e));
-            launch_hint_mac<W>(r, r->stream, po, (const W*)dig, (const W*)hint->dptr, now, D, (const W*)c2crt);
-            HIP_TRY(hipGetLastError());
-            continue;
-        }
-        if (base2 && !split_ring(r) && !r->gen) {                   // BaseBGad: digits computed in the transforms' loader
-            NttCall<W> dc{};
-            dc.op = OP_CRT_BASE2;
-            dc.ring = &dev_ring<W>(r);
-            dc.stream = r->stream;
-            dc.src = reinterpret_cast<const W*>(c2);
-            dc.data = reinterpret_cast<W*>(dig);
-            dc.npoly = now * (size_t)D * (size_t)r->L;
-            dc.b2_first = first; dc.b2_kd = kd; dc.b2_D = D;
-            hipError_t e = dispatch(r->logn, dc);
-            if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("crt_base2 launch: ") + hipGetErrorString(e));
-            launch_hint_mac<W>(r, r->stream, po, (const W*)dig, (const W*)hint->dptr, now, D);
-            HIP_TRY(hipGetLastError());
-            continue;
-        }
+            g.op = GEN_CRTINV; g.ring = &dv; g.gen = &gv; g.stream = r->stream;
+            g.data = c2; g.first_poly = 0; g.npoly = now * (size_t)Ls;
+            if ((rc = launch(g, "general-index crtInv")) != ALCH_OK) return rc;
+        } else if ((rc = do_crt<W>(r, c2, 0, now, true)) != ALCH_OK) return rc;
+        c2pow = c2;
+    }
+    nc.src = gc.src = c2pow;
+    if (s.fused_digits && r->gen) {                               // general index: decompose + reduce in the pass engine's loader
+        gc.op = GEN_CRT_DIGITS;
+        gc.data = dig;
+        gc.npoly = now * (size_t)Ls * (size_t)L;
+        if (s.compact) { gc.src_limbs = Ls; gc.src_first = s.dup; }
+        if ((rc = launch(gc, "general-index crt_digits")) != ALCH_OK) return rc;
+    } else if (s.fused_digits && r->opts.split_fused) {           // split rings: digit transforms + hint products in one kernel (k_ks_accum_split)
+        nc.op = OP_KS_SPLIT;
+        nc.a = diag; nc.hint = hint; nc.out = out; nc.nct = now; nc.dup = s.dup;
+        return launch(r, nc, "ks_accum_split");
+    } else if (s.fused_digits) {                                  // decompose + reduce fused into the digit transforms (k_crt_split_digits)
+        nc.op = OP_CRT_DIGITS;
+        nc.data = dig;
+        nc.npoly = now * (size_t)L * (size_t)L;
+        if ((rc = launch(r, nc, "crt_digits")) != ALCH_OK) return rc;
+    } else if (s.base2 && !split_ring(r) && !r->gen) {            // BaseBGad: digits computed in the transforms' loader
+        nc.op = OP_CRT_BASE2;
+        nc.data = dig;
+        nc.npoly = now * (size_t)s.D * (size_t)L;
+        nc.b2_first = s.first; nc.b2_kd = s.kd; nc.b2_D = s.D;
+        if ((rc = launch(r, nc, "crt_base2")) != ALCH_OK) return rc;
+    } else {
         for (size_t y0 = 0; y0 < now; y0 += 32768) {             // grid.y is 16-bit
             const unsigned ny = (unsigned)std::min<size_t>(32768, now - y0);
-            const W* src = reinterpret_cast<const W*>(c2 + y0 * eb);
-            W* dst = reinterpret_cast<W*>(dig + y0 * D * eb);
-            if (base2)
+            const W* src = c2pow + y0 * elem_words(r);
+            W* dst = dig + y0 * s.D * elem_words(r);
+            if (s.base2)
                 hipLaunchKernelGGL((k_decompose_base2<W>), dim3(ew_grid(elem_words(r)), ny), dim3(256), 0, r->stream,
-                                   dev_ring<W>(r), src, dst, first, kd, D);
+                                   dev_ring<W>(r), src, dst, s.first, s.kd, s.D);
             else
-                hipLaunchKernelGGL((k_decompose_triv<W>), dim3(ew_grid((size_t)r->L * elem_words(r)), ny), dim3(256), 0,
+                hipLaunchKernelGGL((k_decompose_triv<W>), dim3(ew_grid((size_t)L * elem_words(r)), ny), dim3(256), 0,
                                    r->stream, dev_ring<W>(r), src, dst, r->balanced ? 1 : 0);
             HIP_TRY(hipGetLastError());
         }
-        if ((rc = do_crt<W>(r, dig, 0, now * D, false)) != ALCH_OK) return rc;
-        launch_hint_mac<W>(r, r->stream, po, (const W*)dig, (const W*)hint->dptr, now, D);
-        HIP_TRY(hipGetLastError());
+        if ((rc = do_crt<W>(r, dig, 0, now * s.D, false)) != ALCH_OK) return rc;
+    }
+    if (s.compact) launch_hint_mac<W>(r, r->stream, out, dig, hint, now, (u32)Ls, diag, (u32)Ls, (u32)s.dup);
+    else launch_hint_mac<W>(r, r->stream, out, dig, hint, now, s.D, diag);
+    HIP_TRY(hipGetLastError());
+    return ALCH_OK;
+}
+
+// The composed key switch of alch_ct_mul_relin, in chunks of at most scratch_mib of scratch (~1 GiB).  With c2pow, keySwitchQuadCirc's
+// second half for BaseBGad 2 from a c2 that is already on the powerful basis of the hint's ring (mul_full_base2_down):
+// out (c0, c1 on the CRT basis) += sum_d crt(digit_d(c2)) * hint_d.
+template <typename W>
+static int do_mul_relin_unfused(alch_ring* r, const alch_hint* hint, const void* a, const void* b, void* out, size_t batch,
+                                const uint64_t* s_pre, const void* c2pow = nullptr) {
+    KsStage<W> s = ks_stage_plan<W>(r, hint, 0, c2pow != nullptr);
+    const size_t per_ct = s.elems * elem_bytes(r);
+    s.chunk = std::min(batch, std::max<size_t>(1, (r->scratch_mib << 20) / per_ct));
+    int rc = ensure_ws(&r->ws_digits, &r->ws_digits_bytes, s.chunk * per_ct);
+    if (rc != ALCH_OK) return rc;
+    s.scratch = reinterpret_cast<char*>(r->ws_digits);
+    if (!c2pow) scal_to_mont<W>(r, s_pre, 2, s.sr2);
+    const size_t ew = elem_words(r);
+    for (size_t done = 0; done < batch; done += s.chunk) {
+        const size_t now = std::min(s.chunk, batch - done);
+        const W* pa = c2pow ? nullptr : reinterpret_cast<const W*>(a) + done * 2 * ew;
+        const W* pb = c2pow ? nullptr : reinterpret_cast<const W*>(b) + done * 2 * ew;
+        const W* pc = c2pow ? reinterpret_cast<const W*>(c2pow) + done * ew : nullptr;
+        if ((rc = ks_stage<W>(r, s, pa, pb, pc, reinterpret_cast<W*>(out) + done * 2 * ew, now)) != ALCH_OK) return rc;
     }
     return ALCH_OK;
 }
@@ -2403,14 +2485,12 @@ static int do_mul_relin(alch_ring* r, const alch_hint* hint, const void* a, cons
             if (idx >= 2) HIP_TRY(hipStreamWaitEvent(r->aux, r->ev_pb[par], 0));
             c.stream = r->aux;
             c.op = OP_TENSOR_INTT;
-            hipError_t e = dispatch(r->logn, c);
-            if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("tensor_intt launch: ") + hipGetErrorString(e));
+            if ((rc = launch(r, c, "tensor_intt")) != ALCH_OK) return rc;
             HIP_TRY(hipEventRecord(r->ev_pa[par], r->aux));
             HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_pa[par], 0));
             c.stream = r->stream;
             c.op = OP_KS_ACCUM;
-            e = dispatch(r->logn, c);
-            if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("ks_accum launch: ") + hipGetErrorString(e));
+            if ((rc = launch(r, c, "ks_accum")) != ALCH_OK) return rc;
             HIP_TRY(hipEventRecord(r->ev_pb[par], r->stream));
         }
         return ALCH_OK;                                    // the last key switch is on the ring's stream, behind every tensor kernel
@@ -2425,11 +2505,9 @@ static int do_mul_relin(alch_ring* r, const alch_hint* hint, const void* a, cons
         c.out = reinterpret_cast<W*>(out) + done * ct_words;
         c.nct = now;
         c.op = OP_TENSOR_INTT;
-        hipError_t e = dispatch(r->logn, c);
-        if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("tensor_intt launch: ") + hipGetErrorString(e));
+        if ((rc = launch(r, c, "tensor_intt")) != ALCH_OK) return rc;
         c.op = OP_KS_ACCUM;
-        e = dispatch(r->logn, c);
-        if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("ks_accum launch: ") + hipGetErrorString(e));
+        if ((rc = launch(r, c, "ks_accum")) != ALCH_OK) return rc;
     }
     if (two) {
         HIP_TRY(hipEventRecord(r->ev_join, r->aux));
@@ -2463,11 +2541,11 @@ extern "C" int alch_ct_mul_relin(alch_ring* r, const alch_hint* hint, const alch
         if (split_ring(r)) {                 // the split transform works in place: copy first (general-index kernels take src)
             HIP_TRY(hipMemcpyAsync(wa, a->dptr, bytes, hipMemcpyDeviceToDevice, r->stream));
             HIP_TRY(hipMemcpyAsync(wb, b->dptr, bytes, hipMemcpyDeviceToDevice, r->stream));
-            rc = r->word == 4 ? do_crt<u32>(r, wa, 0, 4 * batch, false) : do_crt<u64>(r, wa, 0, 4 * batch, false);
+            rc = ALCH_BY_WORD(r, do_crt, r, wa, 0, 4 * batch, false);
         } else {                             // out of place, straight from the operands
-            rc = r->word == 4 ? do_crt<u32>(r, wa, 0, 2 * batch, false, a->dptr) : do_crt<u64>(r, wa, 0, 2 * batch, false, a->dptr);
+            rc = ALCH_BY_WORD(r, do_crt, r, wa, 0, 2 * batch, false, a->dptr);
             if (rc == ALCH_OK)
-                rc = r->word == 4 ? do_crt<u32>(r, wb, 0, 2 * batch, false, b->dptr) : do_crt<u64>(r, wb, 0, 2 * batch, false, b->dptr);
+                rc = ALCH_BY_WORD(r, do_crt, r, wb, 0, 2 * batch, false, b->dptr);
         }
         if (rc != ALCH_OK) return rc;
         pa = wa;
@@ -2477,11 +2555,9 @@ extern "C" int alch_ct_mul_relin(alch_ring* r, const alch_hint* hint, const alch
     // since round 3 (k_tensor_crtinv_split + k_ks_accum_split<FROM_OPS>); option split_fused < 2 keeps the composed forms
     const bool split_two = split_ring(r) && !r->gen && hint->gadget == ALCH_GAD_TRIV && r->opts.split_fused >= 2;
     if (!split_two && (hint->gadget == ALCH_GAD_BASE2 || split_ring(r) || r->gen))
-        rc = r->word == 4 ? do_mul_relin_unfused<u32>(r, hint, pa, pb, out->dptr, batch, s_pre)
-                          : do_mul_relin_unfused<u64>(r, hint, pa, pb, out->dptr, batch, s_pre);
+        rc = ALCH_BY_WORD(r, do_mul_relin_unfused, r, hint, pa, pb, out->dptr, batch, s_pre);
     else
-        rc = r->word == 4 ? do_mul_relin<u32>(r, hint, pa, pb, out->dptr, batch, s_pre)
-                          : do_mul_relin<u64>(r, hint, pa, pb, out->dptr, batch, s_pre);
+        rc = ALCH_BY_WORD(r, do_mul_relin, r, hint, pa, pb, out->dptr, batch, s_pre);
     if (rc != ALCH_OK) return rc;
     if (flags & ALCH_POW_OUT) return buf_crt(out, 0, 2 * batch, true);
     return ALCH_OK;
@@ -2531,13 +2607,8 @@ static int do_mul_full(alch_ring* rh, alch_ring* rin, alch_ring* rout, const alc
     int rc = ensure_ws(&rh->ws_full, &rh->ws_full_bytes, 2 * pipe_bytes);
     if (rc != ALCH_OK) return rc;
 
-    // s_pre times the moduli the first modSwitch adds
-    uint64_t s_eff[MAXL];
-    for (int j = 0; j < rin->L; ++j) {
-        u64 v = s_pre ? s_pre[j] % rin->q[j] : 1;
-        for (int u = 0; u < dup; ++u) v = h_mulmod(v, rh->q[u] % rin->q[j], rin->q[j]);
-        s_eff[j] = v;
-    }
+    uint64_t s_eff[MAXL];                                  // s_pre times the moduli the first modSwitch adds
+    for (int j = 0; j < rin->L; ++j) s_eff[j] = up_scalar(rh, dup, j + dup, s_pre ? s_pre[j] : 1);
     NttCall<W> c{};
     c.hint = reinterpret_cast<const W*>(hint->dptr);
     c.balanced = rh->balanced;
@@ -2567,22 +2638,19 @@ static int do_mul_full(alch_ring* rh, alch_ring* rin, alch_ring* rout, const alc
         c.a = reinterpret_cast<const W*>(a) + done * in_words;
         c.b = reinterpret_cast<const W*>(b) + done * in_words;
         c.digits = base;
-        hipError_t e = dispatch(rh->logn, c);
-        if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("tensor_intt launch: ") + hipGetErrorString(e));
+        if ((rc = launch(rh, c, "tensor_intt")) != ALCH_OK) return rc;
         // key switch on the hint's ring
         c.op = OP_KS_ACCUM;
         c.ring = &dev_ring<W>(rh);
         c.dup = dup;
         c.out = reinterpret_cast<W*>(base + dig_bytes);
-        e = dispatch(rh->logn, c);
-        if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("ks_accum launch: ") + hipGetErrorString(e));
+        if ((rc = launch(rh, c, "ks_accum")) != ALCH_OK) return rc;
         // modSwitch down
         c.op = OP_RESCALE_OUT;
         c.a = reinterpret_cast<const W*>(base + dig_bytes);
         c.out = reinterpret_cast<W*>(out) + done * out_words;
         c.stash = base + dig_bytes + ks_bytes;
-        e = dispatch(rh->logn, c);
-        if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("rescale_out launch: ") + hipGetErrorString(e));
+        if ((rc = launch(rh, c, "rescale_out")) != ALCH_OK) return rc;
     }
     if (two) {
         HIP_TRY(hipEventRecord(rh->ev_join, rh->aux));
@@ -2591,167 +2659,76 @@ static int do_mul_full(alch_ring* rh, alch_ring* rin, alch_ring* rout, const alc
     return ALCH_OK;
 }
 
-template <typename W> static void gen_suffix_view(alch_ring* r, int u, DevRing<W>& d, GenDev<W>& g);
+// ---- modSwitch down, the two composed forms: both queue on r's stream and write elements of ring_out, a suffix of r ----------
+// CRT-resident form (general index, option rs_lin): the kept limbs stay in the CRT basis (k_gen_rescale_drop / k_gen_rescale_keep):
+// ddn inverse + (L - ddn) forward transforms per component instead of L + (L - ddn).  res: ddn * n words of scratch per element.
+template <typename W>
+static int rescale_down_crt(alch_ring* r, int ddn, const void* in, void* res, void* out, size_t elems, bool dec_c0, bool pow_out) {
+    DropTab<W> dt;
+    fill_drop_tab<W>(r, ddn, dt);
+    const hipError_t e = gen_rescale_lin_dispatch(dev_ring<W>(r), gen_dev<W>(r), reinterpret_cast<const W*>(in), reinterpret_cast<W*>(res),
+                                                  reinterpret_cast<W*>(out), dt, dec_c0 ? 1 : 0, elems, r->stream, pow_out);
+    return e == hipSuccess ? ALCH_OK : fail(ALCH_E_HIP, std::string("rescale launch: ") + hipGetErrorString(e));
+}
 
-// The same mul_ for rings whose polynomial does not fit one LDS-resident transform (split crt, n = 2^16 / 2^15):
-// composed from the element-wise kernels and batched transforms, one ciphertext chunk at a time.
+// Limb-at-a-time form.  cur: per * now elements of r on the Pow basis; c0 of every pair goes onto the Dec basis first for a general index
+// (dec_c0, per = 2: rescaleDec).  The limbs are dropped outermost first through ping / pong (per * now elements each), the last step
+// writes elements per * first .. of `out`; then back to the CRT basis on ring_out (same device tables as r's: queued on r's stream).
+template <typename W>
+static int rescale_down_limbs(alch_ring* r, alch_ring* rout, char* cur, char* ping, char* pong, void* out, size_t first, size_t now,
+                              size_t per, bool dec_c0, bool pow_out) {
+    const int ddn = r->L - rout->L;
+    int rc;
+    if (dec_c0 && (rc = do_columns<W>(r, GEN_LINV, cur, 0, now, 2)) != ALCH_OK) return rc;
+    for (int u = 0; u < ddn; ++u) {
+        char* nxt = (u + 1 == ddn) ? reinterpret_cast<char*>(out) + first * per * elem_bytes(rout) : ((u & 1) ? pong : ping);
+        const DevRing<W> rs = suffix_view<W>(r, u);
+        const size_t total = per * now * (size_t)(rs.L - 1) * r->n;
+        hipLaunchKernelGGL((k_rescale_drop0<W>), dim3(ew_grid(total)), dim3(256), 0, r->stream, rs, (const W*)cur, (W*)nxt, per * now,
+                           drop0_inv_mont<W>(r, u));
+        HIP_TRY(hipGetLastError());
+        cur = nxt;
+    }
+    if (dec_c0 && (rc = do_columns<W>(rout, GEN_L, out, 2 * first, now, 2, r->stream)) != ALCH_OK) return rc;
+    if (!pow_out && (rc = do_crt<W>(rout, out, per * first, per * now, false, nullptr, r->stream)) != ALCH_OK) return rc;
+    return ALCH_OK;
+}
+
+// The same mul_ for rings whose polynomial does not fit one LDS-resident transform (split crt, n = 2^16 / 2^15) and for general-index
+// rings: the composed key switch on ring_h, then one of the composed modSwitch forms, one ciphertext chunk at a time.
 template <typename W>
 static int do_mul_full_unfused(alch_ring* rh, alch_ring* rin, alch_ring* rout, const alch_hint* hint, const void* a,
                                const void* b, void* out, size_t batch, const uint64_t* s_pre, bool pow_out) {
     const int L = rh->L, dup = L - rin->L, ddn = L - rout->L;
     const size_t eb = elem_bytes(rh);
-    // scratch per ciphertext: key-switched pair (2) + c2 in both bases (2) + digits (L) + rescale ping-pong (2 + 2), in ring_h elements
-    const bool no_digits = (!rh->gen && rh->opts.split_fused) || gen_ks_fused(rh, hint);    // one-kernel key switch: no digits in HBM
-    const size_t dig_elems = no_digits ? 0 : (size_t)L;
-    const size_t per_ct = (size_t)(2 + 2 + 4 + dig_elems) * eb;
-    size_t chunk = std::max<size_t>(1, (rh->scratch_mib << 20) / per_ct);
-    chunk = std::min(chunk, batch);
+    // scratch per ciphertext: key-switched pair (2) + the key-switch stage's (c2 in both bases + L digits, fewer for its one-kernel
+    // forms) + rescale ping-pong (2 + 2), in ring_h elements
+    KsStage<W> s = ks_stage_plan<W>(rh, hint, dup, false);
+    const size_t per_ct = (2 + s.elems + 4) * eb;
+    const size_t chunk = std::min(batch, std::max<size_t>(1, (rh->scratch_mib << 20) / per_ct));
     int rc = ensure_ws(&rh->ws_full, &rh->ws_full_bytes, chunk * per_ct);
     if (rc != ALCH_OK) return rc;
     char* ks = reinterpret_cast<char*>(rh->ws_full);
-    char* c2 = ks + chunk * 2 * eb;
-    char* c2crt = c2 + chunk * eb;
-    char* dig = c2crt + chunk * eb;
-    char* ping = dig + chunk * dig_elems * eb;
+    s.scratch = ks + chunk * 2 * eb;
+    s.chunk = chunk;
+    char* ping = s.scratch + chunk * s.elems * eb;
     char* pong = ping + chunk * 2 * eb;
-    uint64_t s_eff[MAXL];
-    for (int j = 0; j < rin->L; ++j) {
-        u64 v = s_pre ? s_pre[j] % rin->q[j] : 1;
-        for (int u = 0; u < dup; ++u) v = h_mulmod(v, rh->q[u] % rin->q[j], rin->q[j]);
-        s_eff[j] = v;
-    }
-    Scal<W> sr2;
-    scal_to_mont<W>(rin, s_eff, 2, sr2);
-    GTab<W> gt{};
-    if (rh->gen) for (int j = 0; j < L; ++j) gt.p[j] = rh->gh.rad > 1 ? gen_dev<W>(rh).gcrt[j] : nullptr;
+    uint64_t s_eff[MAXL];                                  // s_pre times the moduli the first modSwitch adds
+    for (int j = 0; j < rin->L; ++j) s_eff[j] = up_scalar(rh, dup, j + dup, s_pre ? s_pre[j] : 1);
+    scal_to_mont<W>(rin, s_eff, 2, s.sr2);
     const bool dec_c0 = rh->gen && rh->gh.rad > 1;     // general index: modSwitch rescales c0 on the Dec basis (rescaleDec), c1 on Pow
-    // DevRing of the suffix ring that starts at limb u of ring_h
-    auto suffix = [&](int u) {
-        DevRing<W> d = dev_ring<W>(rh);
-        d.L = L - u;
-        for (int j = 0; j + u < L; ++j) {
-            d.mod[j] = d.mod[j + u]; d.ninv_m[j] = d.ninv_m[j + u]; d.w1ninv_m[j] = d.w1ninv_m[j + u];
-            d.twf[j] = d.twf[j + u]; d.twi[j] = d.twi[j + u]; d.twp[j] = d.twp[j + u];
-            d.tws[j] = d.tws[j + u]; d.twsi[j] = d.twsi[j + u];
-        }
-        return d;
-    };
-    const size_t in_bytes = 2 * elem_bytes(rin), out_bytes = 2 * elem_bytes(rout);
+    const size_t in_words = 2 * elem_words(rin), out_bytes = 2 * elem_bytes(rout);
     for (size_t done = 0; done < batch; done += chunk) {
         const size_t now = std::min(chunk, batch - done);
-        const W* pa = reinterpret_cast<const W*>(reinterpret_cast<const char*>(a) + done * in_bytes);
-        const W* pb = reinterpret_cast<const W*>(reinterpret_cast<const char*>(b) + done * in_bytes);
-        const size_t words = now * elem_words(rh);
-        // (*) and modSwitch up
-        bool fused_ks = false, split_done = false;
-        if constexpr (sizeof(W) == 4) {
-            if (gen_ks_fused(rh, hint)) {
-                if ((rc = launch_gen_ks(rh, hint, pa, pb, reinterpret_cast<u32*>(ks), reinterpret_cast<u32*>(c2), now, dup, sr2, rh->stream)) != ALCH_OK) return rc;
-                fused_ks = true;
-            }
-        }
-        if (!fused_ks) {
-        // general index below the hint's ring: the limbs the first modSwitch adds are zero in c2, so c2, its crtInv and its digits
-        // are kept on the operands' L - dup limbs only (a fifth to a half of the digit transforms of PT2CT's products)
-        const bool c2_compact = rh->gen && dup > 0;
-        const int Ls = L - dup;
-        ALCH_LAUNCH_VW(k_tensor_ew, rh, words, rh->stream, dev_ring<W>(rh), pa, pb, (W*)ks,
-                           (W*)c2, now, sr2, dup, (W*)c2crt, gt, c2_compact ? 1 : 0);
-        HIP_TRY(hipGetLastError());
-        // keySwitchQuadCirc on ring_h
-        if (c2_compact) {
-            DevRing<W> dv; GenDev<W> gv;
-            gen_suffix_view<W>(rh, dup, dv, gv);
-            GenCall<W> g{};
-            g.op = GEN_CRTINV; g.ring = &dv; g.gen = &gv; g.stream = rh->stream;
-            g.data = reinterpret_cast<W*>(c2); g.first_poly = 0; g.npoly = now * (size_t)Ls;
-            hipError_t e = gen_dispatch(g);
-            if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("general-index crtInv launch: ") + hipGetErrorString(e));
-        } else if ((rc = do_crt<W>(rh, c2, 0, now, true)) != ALCH_OK) return rc;
-        if (rh->gen) {
-            GenCall<W> g{};
-            g.op = GEN_CRT_DIGITS;
-            g.ring = &dev_ring<W>(rh);
-            g.gen = &gen_dev<W>(rh);
-            g.stream = rh->stream;
-            g.src = reinterpret_cast<const W*>(c2);
-            g.data = reinterpret_cast<W*>(dig);
-            g.npoly = now * (size_t)(c2_compact ? Ls : L) * (size_t)L;
-            g.balanced = rh->balanced;
-            if (c2_compact) { g.src_limbs = Ls; g.src_first = dup; }
-            hipError_t e = gen_dispatch(g);
-            if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("general-index crt_digits launch: ") + hipGetErrorString(e));
-        } else if (rh->opts.split_fused) {   // digit transforms + hint products in one kernel (k_ks_accum_split)
-            NttCall<W> dc{};
-            dc.op = OP_KS_SPLIT;
-            dc.ring = &dev_ring<W>(rh);
-            dc.stream = rh->stream;
-            dc.src = reinterpret_cast<const W*>(c2);
-            dc.a = reinterpret_cast<const W*>(c2crt);
-            dc.hint = reinterpret_cast<const W*>(hint->dptr);
-            dc.out = reinterpret_cast<W*>(ks);
-            dc.nct = now;
-            dc.dup = dup;
-            dc.balanced = rh->balanced;
-            hipError_t e = dispatch(rh->logn, dc);
-            if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("ks_accum_split launch: ") + hipGetErrorString(e));
-            split_done = true;
-        } else {   // decompose + reduce fused into the digit transforms (k_crt_split_digits)
-            NttCall<W> dc{};
-            dc.op = OP_CRT_DIGITS;
-            dc.ring = &dev_ring<W>(rh);
-            dc.stream = rh->stream;
-            dc.src = reinterpret_cast<const W*>(c2);
-            dc.data = reinterpret_cast<W*>(dig);
-            dc.npoly = now * (size_t)L * (size_t)L;
-            dc.balanced = rh->balanced;
-            hipError_t e = dispatch(rh->logn, dc);
-            if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("crt_digits launch: ") + hipGetErrorString(e));
-        }
-        if (!split_done) {
-        if (c2_compact) launch_hint_mac<W>(rh, rh->stream, (W*)ks, (const W*)dig, (const W*)hint->dptr, now, (u32)Ls, (const W*)c2crt, (u32)Ls, (u32)dup);
-        else launch_hint_mac<W>(rh, rh->stream, (W*)ks, (const W*)dig, (const W*)hint->dptr, now, (u32)L, (const W*)c2crt);
-        HIP_TRY(hipGetLastError());
-        }
-        }
-        if (rh->gen && rh->opts.rs_lin && !pow_out) {
-            // modSwitch down with the kept limbs in the CRT basis (k_gen_rescale_drop / k_gen_rescale_keep): ddn inverse +
-            // (L - ddn) forward transforms per component instead of L + (L - ddn)
-            DropTab<W> dt;
-            fill_drop_tab<W>(rh, ddn, dt);
-            hipError_t e = gen_rescale_lin_dispatch(dev_ring<W>(rh), gen_dev<W>(rh), reinterpret_cast<const W*>(ks), reinterpret_cast<W*>(ping),
-                                                    reinterpret_cast<W*>(reinterpret_cast<char*>(out) + done * out_bytes), dt, dec_c0 ? 1 : 0,
-                                                    2 * now, rh->stream);
-            if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("rescale launch: ") + hipGetErrorString(e));
-            continue;
-        }
-        // modSwitch down: Pow basis (c0: Dec basis for a general index), one limb at a time, then back to the CRT basis on ring_out
-        if ((rc = do_crt<W>(rh, ks, 0, 2 * now, true)) != ALCH_OK) return rc;
-        if (dec_c0 && (rc = do_columns<W>(rh, GEN_LINV, ks, 0, now, 2)) != ALCH_OK) return rc;
-        char* cur = ks;
-        for (int u = 0; u < ddn; ++u) {
-            char* nxt = (u + 1 == ddn) ? reinterpret_cast<char*>(out) + done * out_bytes : ((u & 1) ? pong : ping);
-            const DevRing<W> rs = suffix(u);
-            uint64_t inv[MAXL] = {0};
-            Scal<W> sm;
-            for (int j = 0; j < MAXL; ++j) sm.v[j] = 0;
-            const int bits = 8 * (int)sizeof(W);
-            for (int j = 1; j < rs.L; ++j) {
-                const u64 qj = rh->q[u + j];
-                inv[j] = h_powmod(rh->q[u] % qj, qj - 2, qj);
-                sm.v[j] = (W)h_mulmod(inv[j], h_powmod(2, (u64)bits, qj), qj);
-            }
-            const size_t total = 2 * now * (size_t)(rs.L - 1) * rh->n;
-            hipLaunchKernelGGL((k_rescale_drop0<W>), dim3(ew_grid(total)), dim3(256), 0, rh->stream, rs, (const W*)cur, (W*)nxt,
-                               2 * now, sm);
-            HIP_TRY(hipGetLastError());
-            cur = nxt;
-        }
-        if (dec_c0 && (rc = do_columns<W>(rout, GEN_L, out, 2 * done, now, 2, rh->stream)) != ALCH_OK) return rc;
-        if (!pow_out) {
-            // crt on ring_out, queued on ring_h's stream (same device tables: ring_out is a suffix of ring_h)
-            if ((rc = do_crt<W>(rout, out, 2 * done, 2 * now, false, nullptr, rh->stream)) != ALCH_OK) return rc;
-        }
+        // (*), modSwitch up and keySwitchQuadCirc on ring_h
+        if ((rc = ks_stage<W>(rh, s, reinterpret_cast<const W*>(a) + done * in_words, reinterpret_cast<const W*>(b) + done * in_words, nullptr,
+                              reinterpret_cast<W*>(ks), now)) != ALCH_OK) return rc;
+        // modSwitch down
+        if (rh->gen && rh->opts.rs_lin && !pow_out)
+            rc = rescale_down_crt<W>(rh, ddn, ks, ping, reinterpret_cast<char*>(out) + done * out_bytes, 2 * now, dec_c0, false);
+        else if ((rc = do_crt<W>(rh, ks, 0, 2 * now, true)) == ALCH_OK)          // to the Pow basis first
+            rc = rescale_down_limbs<W>(rh, rout, ks, ping, pong, out, done, now, 2, dec_c0, pow_out);
+        if (rc != ALCH_OK) return rc;
     }
     return ALCH_OK;
 }
@@ -2771,47 +2748,6 @@ static bool is_suffix_ring(const alch_ring* small, const alch_ring* big) {
 // p + MulPNoise): mul_full_base2_down below.
 template <typename W> static int do_mod_switch(alch_ring* rin, alch_ring* rout, const void* in, void* out, size_t batch, unsigned flags, int per = 2);
 
-// keySwitchQuadCirc's second half for BaseBGad 2, from a c2 that is already on the powerful basis of the hint's ring:
-// ks (c0, c1 on the CRT basis) += sum_d crt(digit_d(c2)) * hint_d.  The same kernels as do_mul_relin_unfused's base-2 branches.
-template <typename W>
-static int ks_base2_from_pow(alch_ring* r, const alch_hint* hint, void* ks, const void* c2pow, size_t batch) {
-    Scal<u32> first, kd;
-    const u32 D = (u32)base2_layout(r, first, kd);
-    const size_t eb = elem_bytes(r);
-    size_t chunk = std::min(batch, std::max<size_t>(1, (r->scratch_mib << 20) / ((size_t)D * eb)));
-    int rc = ensure_ws(&r->ws_digits, &r->ws_digits_bytes, chunk * D * eb);
-    if (rc != ALCH_OK) return rc;
-    char* dig = reinterpret_cast<char*>(r->ws_digits);
-    for (size_t done = 0; done < batch; done += chunk) {
-        const size_t now = std::min(chunk, batch - done);
-        const char* c2 = reinterpret_cast<const char*>(c2pow) + done * eb;
-        W* po = reinterpret_cast<W*>(reinterpret_cast<char*>(ks) + done * 2 * eb);
-        if (!split_ring(r) && !r->gen) {                             // digits computed in the transforms' loader
-            NttCall<W> dc{};
-            dc.op = OP_CRT_BASE2;
-            dc.ring = &dev_ring<W>(r);
-            dc.stream = r->stream;
-            dc.src = reinterpret_cast<const W*>(c2);
-            dc.data = reinterpret_cast<W*>(dig);
-            dc.npoly = now * (size_t)D * (size_t)r->L;
-            dc.b2_first = first; dc.b2_kd = kd; dc.b2_D = D;
-            hipError_t e = dispatch(r->logn, dc);
-            if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("crt_base2 launch: ") + hipGetErrorString(e));
-        } else {
-            for (size_t y0 = 0; y0 < now; y0 += 32768) {             // grid.y is 16-bit
-                const unsigned ny = (unsigned)std::min<size_t>(32768, now - y0);
-                hipLaunchKernelGGL((k_decompose_base2<W>), dim3(ew_grid(elem_words(r)), ny), dim3(256), 0, r->stream, dev_ring<W>(r),
-                                   reinterpret_cast<const W*>(c2 + y0 * eb), reinterpret_cast<W*>(dig + y0 * D * eb), first, kd, D);
-                HIP_TRY(hipGetLastError());
-            }
-            if ((rc = do_crt<W>(r, dig, 0, now * D, false)) != ALCH_OK) return rc;
-        }
-        launch_hint_mac<W>(r, r->stream, po, (const W*)dig, (const W*)hint->dptr, now, D);
-        HIP_TRY(hipGetLastError());
-    }
-    return ALCH_OK;
-}
-
 // mul_ under a BaseBGad 2 hint that lives on FEWER limbs than the operands (PT2CT.hs:140,164: the product sits at p + MulPNoise units
 // rounded up to whole limbs, the hint at p + KSAccumPNoise): the leading modSwitch goes DOWN on the quadratic ciphertext -- c0 on the
 // decoding basis, c1 and c2 on the powerful basis -- before the key switch.
@@ -2820,18 +2756,16 @@ static int mul_full_base2_down(const alch_hint* hint, alch_ring* rin, alch_ring*
                                const uint64_t* s_pre, alch_buf* t, alch_buf* c2, alch_buf* c2h) {
     Scal<W> sr2;
     scal_to_mont<W>(rin, s_pre, 2, sr2);
-    GTab<W> gt{};
-    if (rin->gen) for (int j = 0; j < rin->L; ++j) gt.p[j] = rin->gh.rad > 1 ? gen_dev<W>(rin).gcrt[j] : nullptr;
     const size_t words = batch * elem_words(rin);
     // the tensor product and both rescales run on the operands' stream, the key switch on the hint's
     ALCH_LAUNCH_VW(k_tensor_ew, rin, words, rin->stream, dev_ring<W>(rin), (const W*)a, (const W*)b, (W*)t->dptr, (W*)c2->dptr, batch, sr2, 0,
-                   (W*)nullptr, gt);
+                   (W*)nullptr, g_table<W>(rin));
     HIP_TRY(hipGetLastError());
     int rc;
     if ((rc = do_mod_switch<W>(rin, rh, t->dptr, ks, batch, 0)) != ALCH_OK) return rc;
     if ((rc = do_mod_switch<W>(rin, rh, c2->dptr, c2h->dptr, batch, ALCH_POW_OUT, 1)) != ALCH_OK) return rc;
     HIP_TRY(hipStreamSynchronize(rin->stream));
-    return ks_base2_from_pow<W>(rh, hint, ks, c2h->dptr, batch);
+    return do_mul_relin_unfused<W>(rh, hint, nullptr, nullptr, ks, batch, nullptr, c2h->dptr);
 }
 static int mul_full_base2(const alch_hint* hint, const alch_buf* a, const alch_buf* b, alch_buf* out, size_t batch, const uint64_t* s_pre,
                           unsigned flags) {
@@ -2864,18 +2798,13 @@ static int mul_full_base2(const alch_hint* hint, const alch_buf* a, const alch_b
     HIP_TRY(hipStreamSynchronize(rin->stream));
     HIP_TRY(hipStreamSynchronize(rout->stream));
     const alch_buf *pa = a, *pb = b;
-    uint64_t s_eff[MAXL];
-    for (int j = 0; j < rh->L; ++j) s_eff[j] = 1;
-    for (int j = dup; j < rh->L; ++j) {
-        u64 v = s_pre ? s_pre[j - dup] % rh->q[j] : 1;
-        for (int u = 0; u < dup; ++u) v = h_mulmod(v, h_invmod(rh->q[u] % rh->q[j], rh->q[j]), rh->q[j]);
-        s_eff[j] = v;
-    }
+    uint64_t s_eff[MAXL];                                      // s_pre / q_a: each switched-up operand carries the added moduli, the product needs them once
+    for (int j = 0; j < rh->L; ++j) s_eff[j] = j < dup ? 1 : up_scalar(rh, dup, j, s_pre ? s_pre[j - dup] : 1, true);
     if (dup > 0) {
         if ((rc = alch_buf_alloc(rh, 2 * batch, &ua)) != ALCH_OK || (rc = alch_buf_alloc(rh, 2 * batch, &ub)) != ALCH_OK) return done(rc);
         // alch_ct_mod_switch up works on rout's stream = rh's here
-        rc = rh->word == 4 ? do_mod_switch<u32>(rin, rh, a->dptr, ua->dptr, batch, 0) : do_mod_switch<u64>(rin, rh, a->dptr, ua->dptr, batch, 0);
-        if (rc == ALCH_OK) rc = rh->word == 4 ? do_mod_switch<u32>(rin, rh, b->dptr, ub->dptr, batch, 0) : do_mod_switch<u64>(rin, rh, b->dptr, ub->dptr, batch, 0);
+        rc = ALCH_BY_WORD(rh, do_mod_switch, rin, rh, a->dptr, ua->dptr, batch, 0);
+        if (rc == ALCH_OK) rc = ALCH_BY_WORD(rh, do_mod_switch, rin, rh, b->dptr, ub->dptr, batch, 0);
         if (rc != ALCH_OK) return done(rc);
         pa = ua; pb = ub;
     }
@@ -2887,18 +2816,15 @@ static int mul_full_base2(const alch_hint* hint, const alch_buf* a, const alch_b
         if ((rc = alch_buf_alloc(rin, 2 * batch, &ua)) != ALCH_OK || (rc = alch_buf_alloc(rin, batch, &ub)) != ALCH_OK ||
             (rc = alch_buf_alloc(rh, batch, &c2h)) != ALCH_OK) return done(rc);
         HIP_TRY(hipStreamSynchronize(rh->stream));
-        rc = rh->word == 4 ? mul_full_base2_down<u32>(hint, rin, rh, a->dptr, b->dptr, ks->dptr, batch, s_pre, ua, ub, c2h)
-                           : mul_full_base2_down<u64>(hint, rin, rh, a->dptr, b->dptr, ks->dptr, batch, s_pre, ua, ub, c2h);
+        rc = ALCH_BY_WORD(rh, mul_full_base2_down, hint, rin, rh, a->dptr, b->dptr, ks->dptr, batch, s_pre, ua, ub, c2h);
     } else
-    rc = rh->word == 4 ? do_mul_relin_unfused<u32>(rh, hint, pa->dptr, pb->dptr, ks->dptr, batch, s_eff)
-                       : do_mul_relin_unfused<u64>(rh, hint, pa->dptr, pb->dptr, ks->dptr, batch, s_eff);
+        rc = ALCH_BY_WORD(rh, do_mul_relin_unfused, rh, hint, pa->dptr, pb->dptr, ks->dptr, batch, s_eff);
     if (rc != ALCH_OK) return done(rc);
     if (down) {
-        rc = rh->word == 4 ? do_mod_switch<u32>(rh, rout, ks->dptr, out->dptr, batch, flags & ALCH_POW_OUT)
-                           : do_mod_switch<u64>(rh, rout, ks->dptr, out->dptr, batch, flags & ALCH_POW_OUT);
+        rc = ALCH_BY_WORD(rh, do_mod_switch, rh, rout, ks->dptr, out->dptr, batch, flags & ALCH_POW_OUT);
     } else if (flags & ALCH_POW_OUT) {
         HIP_TRY(hipMemcpyAsync(out->dptr, ks->dptr, 2 * batch * elem_bytes(rh), hipMemcpyDeviceToDevice, rh->stream));
-        rc = rh->word == 4 ? do_crt<u32>(rh, out->dptr, 0, 2 * batch, true) : do_crt<u64>(rh, out->dptr, 0, 2 * batch, true);
+        rc = ALCH_BY_WORD(rh, do_crt, rh, out->dptr, 0, 2 * batch, true);
     }
     if (rc != ALCH_OK) return done(rc);
     HIP_TRY(hipStreamSynchronize(rh->stream));                 // the scratch buffers are freed on return
@@ -2921,29 +2847,20 @@ extern "C" int alch_ct_mul_full(const alch_hint* hint, const alch_buf* a, const 
     BIND(rh);
     if (!pairs_ok(batch, a->n_elems) || !pairs_ok(batch, b->n_elems) || !pairs_ok(batch, out->n_elems))
         return fail(ALCH_E_INVALID, "buffers must hold 2*batch ring elements");
-    if (!rh->ev_x) HIP_TRY(hipEventCreateWithFlags(&rh->ev_x, hipEventDisableTiming));
-    if (rin->stream != rh->stream) {
-        HIP_TRY(hipEventRecord(rh->ev_x, rin->stream));
-        HIP_TRY(hipStreamWaitEvent(rh->stream, rh->ev_x, 0));
-    }
-    if (rout->stream != rh->stream && rout->stream != rin->stream) {
-        HIP_TRY(hipEventRecord(rh->ev_x, rout->stream));
-        HIP_TRY(hipStreamWaitEvent(rh->stream, rh->ev_x, 0));
-    }
-    const bool pow_out = (flags & ALCH_POW_OUT) != 0;
+    // everything runs on the hint ring's stream, behind the work of the other two rings (one wait serves both where they share a stream)
+    const bool two_others = rout->stream != rin->stream;
     int rc;
+    if ((rc = ext_order(rh, rin, true)) != ALCH_OK) return rc;
+    if (two_others && (rc = ext_order(rh, rout, true)) != ALCH_OK) return rc;
+    const bool pow_out = (flags & ALCH_POW_OUT) != 0;
     if (!rh->has_crt) return fail(ALCH_E_NO_CRT, "the hint's ring has no CRT basis");
     if (split_ring(rh) || rh->gen)
-        rc = rh->word == 4 ? do_mul_full_unfused<u32>(rh, rin, rout, hint, a->dptr, b->dptr, out->dptr, batch, s_pre, pow_out)
-                           : do_mul_full_unfused<u64>(rh, rin, rout, hint, a->dptr, b->dptr, out->dptr, batch, s_pre, pow_out);
+        rc = ALCH_BY_WORD(rh, do_mul_full_unfused, rh, rin, rout, hint, a->dptr, b->dptr, out->dptr, batch, s_pre, pow_out);
     else
-        rc = rh->word == 4 ? do_mul_full<u32>(rh, rin, rout, hint, a->dptr, b->dptr, out->dptr, batch, s_pre, pow_out)
-                           : do_mul_full<u64>(rh, rin, rout, hint, a->dptr, b->dptr, out->dptr, batch, s_pre, pow_out);
+        rc = ALCH_BY_WORD(rh, do_mul_full, rh, rin, rout, hint, a->dptr, b->dptr, out->dptr, batch, s_pre, pow_out);
     if (rc != ALCH_OK) return rc;
-    HIP_TRY(hipEventRecord(rh->ev_x, rh->stream));
-    if (rin->stream != rh->stream) HIP_TRY(hipStreamWaitEvent(rin->stream, rh->ev_x, 0));
-    if (rout->stream != rh->stream) HIP_TRY(hipStreamWaitEvent(rout->stream, rh->ev_x, 0));
-    return ALCH_OK;
+    if ((rc = ext_order(rh, rin, false)) != ALCH_OK) return rc;
+    return two_others ? ext_order(rh, rout, false) : ALCH_OK;
 } catch (...) { return abi_catch(); }
 
 // ------------------------------------------------------------------------------------------------------
@@ -3022,8 +2939,8 @@ extern "C" int alch_tunnel_create(alch_ring* rr, alch_ring* rs, int gadget, cons
         }
         BIND(rs);
     }
-    rc = rs->word == 4 ? tunnel_to_mont<u32>(rs, t->lin, lin_crt->dptr, nlin) : tunnel_to_mont<u64>(rs, t->lin, lin_crt->dptr, nlin);
-    if (rc == ALCH_OK) rc = rs->word == 4 ? tunnel_to_mont<u32>(rs, t->ks, ks_crt->dptr, nks) : tunnel_to_mont<u64>(rs, t->ks, ks_crt->dptr, nks);
+    rc = ALCH_BY_WORD(rs, tunnel_to_mont, rs, t->lin, lin_crt->dptr, nlin);
+    if (rc == ALCH_OK) rc = ALCH_BY_WORD(rs, tunnel_to_mont, rs, t->ks, ks_crt->dptr, nks);
     if (rc != ALCH_OK) { alch_tunnel_free(t); return rc; }
     if (hipStreamSynchronize(rs->stream) != hipSuccess) { alch_tunnel_free(t); return fail(ALCH_E_HIP, "tunnel setup failed"); }
     *out = t;
@@ -3043,19 +2960,6 @@ extern "C" int alch_tunnel_free(alch_tunnel* t) try {
     delete t;
     return ALCH_OK;
 } catch (...) { return abi_catch(); }
-
-// View of the last L - u limbs of a general-index ring (device tables shared with the ring itself).
-template <typename W>
-static void gen_suffix_view(alch_ring* r, int u, DevRing<W>& d, GenDev<W>& g) {
-    d = dev_ring<W>(r);
-    g = gen_dev<W>(r);
-    d.L = r->L - u;
-    for (int j = 0; j + u < r->L; ++j) {
-        d.mod[j] = d.mod[j + u];
-        g.tabf[j] = g.tabf[j + u]; g.tabi[j] = g.tabi[j + u]; g.iscale_m[j] = g.iscale_m[j + u];
-        g.gcrt[j] = g.gcrt[j + u]; g.gcrt_inv[j] = g.gcrt_inv[j + u]; g.radinv_m[j] = g.radinv_m[j + u];
-    }
-}
 
 // SymmSHE.tunnel on a batch of linear ciphertexts (k = 0):  out = (f'(c0), 0) + sum_i switch(hint_i, embed(c1_i)).
 // rin: the ring the ciphertexts live in -- the tunnel's R' ring or its last limbs (PT2CT emits modSwitch_ .: tunnel_ hint .: modSwitch_,
@@ -3095,15 +2999,13 @@ static int do_tunnel(const alch_tunnel* t, alch_ring* rin, const void* in, void*
     char* x1 = x0 + chunk * D * ebx;
     char* dig = x1 + chunk * D * ebx;
     uint64_t s_eff[MAXL] = {0};
-    for (int j = dup; j < L; ++j) {
-        u64 v = s_pre ? s_pre[j] % rs->q[j] : 1;
-        for (int u = 0; u < dup; ++u) v = h_mulmod(v, rs->q[u] % rs->q[j], rs->q[j]);      // modSwitch up: times the added moduli
-        s_eff[j] = v;
-    }
+    for (int j = dup; j < L; ++j) s_eff[j] = up_scalar(rs, dup, j, s_pre ? s_pre[j] : 1);      // modSwitch up: times the added moduli
     const bool scale = s_pre != nullptr || dup > 0;
     Scal<W> sm;
     scal_to_mont<W>(rs, s_eff, 1, sm);
     const bool dec_c0 = rr->gh.rad > 1 && t->linv_skip_mask != ((1u << rr->gh.nfact) - 1);
+    GenCall<W> gx{};                                 // what the pass-engine launches on rx share
+    gx.ring = &dev_ring<W>(rx); gx.gen = &gen_dev<W>(rx); gx.stream = rs->stream;
     for (size_t done = 0; done < batch; done += chunk) {
         const size_t now = std::min(chunk, batch - done);
         const char* src = reinterpret_cast<const char*>(in) + done * 2 * ebr;
@@ -3117,8 +3019,7 @@ static int do_tunnel(const alch_tunnel* t, alch_ring* rin, const void* in, void*
             g.data = reinterpret_cast<W*>(win); g.src = pin ? reinterpret_cast<const W*>(src) : nullptr;
             g.elem_stride = 2; g.first_poly = 0; g.npoly = now * (size_t)rin->L;
             g.skip_mask = t->linv_skip_mask; g.fail_flag = rin->d_flag;
-            hipError_t e = gen_dispatch(g);
-            if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("tunnel lInv launch: ") + hipGetErrorString(e));
+            if ((rc = launch(g, "tunnel lInv")) != ALCH_OK) return rc;
         }
         const W* in0 = (pin && !dec_c0) ? reinterpret_cast<const W*>(src) : reinterpret_cast<const W*>(win);
         const W* in1 = pin ? reinterpret_cast<const W*>(src) : reinterpret_cast<const W*>(win);
@@ -3133,8 +3034,7 @@ static int do_tunnel(const alch_tunnel* t, alch_ring* rin, const void* in, void*
             GenCall<W> g{};
             g.op = GEN_CRT; g.ring = &dv; g.gen = &gv; g.stream = rs->stream;
             g.data = reinterpret_cast<W*>(x0); g.first_poly = 0; g.npoly = now * (size_t)D * Lx;
-            hipError_t e = gen_dispatch(g);
-            if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("tunnel crt launch: ") + hipGetErrorString(e));
+            if ((rc = launch(g, "tunnel crt")) != ALCH_OK) return rc;
         } else if ((rc = do_crt<W>(rx, x0, 0, now * D, false, nullptr, rs->stream)) != ALCH_OK) return rc;
         W* po = reinterpret_cast<W*>(reinterpret_cast<char*>(out) + done * 2 * ebs);
         // k_tunnel_mac_e starts its accumulators from evalLin's constant term itself: no pass for it then
@@ -3156,20 +3056,16 @@ static int do_tunnel(const alch_tunnel* t, alch_ring* rin, const void* in, void*
             continue;
         }
         if (base2) {                                 // BaseBGad 2 (examples/Tunnel.hs:24): decompose + reduce in the transforms' loader
-            GenCall<W> g{};
-            g.op = GEN_CRT_BASE2; g.ring = &dev_ring<W>(rx); g.gen = &gen_dev<W>(rx); g.stream = rs->stream;
-            g.src = reinterpret_cast<const W*>(x1); g.data = reinterpret_cast<W*>(dig);
+            GenCall<W> g = gx;
+            g.op = GEN_CRT_BASE2; g.src = reinterpret_cast<const W*>(x1); g.data = reinterpret_cast<W*>(dig);
             g.npoly = now * (size_t)D * (size_t)GD * (size_t)L; g.b2_first = b2first; g.b2_kd = b2kd; g.b2_D = GD;
-            hipError_t e = gen_dispatch(g);
-            if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("tunnel base2 crt_digits launch: ") + hipGetErrorString(e));
+            if ((rc = launch(g, "tunnel base2 crt_digits")) != ALCH_OK) return rc;
         } else {
-            GenCall<W> g{};
-            g.op = GEN_CRT_DIGITS; g.ring = &dev_ring<W>(rx); g.gen = &gen_dev<W>(rx); g.stream = rs->stream;
-            g.src = reinterpret_cast<const W*>(x1); g.data = reinterpret_cast<W*>(dig);
+            GenCall<W> g = gx;
+            g.op = GEN_CRT_DIGITS; g.src = reinterpret_cast<const W*>(x1); g.data = reinterpret_cast<W*>(dig);
             g.npoly = now * (size_t)D * (size_t)Lx * (size_t)L; g.balanced = rs->balanced; g.with_diag = true;
             g.src_limbs = (int)Lx; g.src_first = (int)xoff;
-            hipError_t e = gen_dispatch(g);
-            if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("tunnel crt_digits launch: ") + hipGetErrorString(e));
+            if ((rc = launch(g, "tunnel crt_digits")) != ALCH_OK) return rc;
         }
         if (mac_e) {
             if constexpr (sizeof(W) == 4) {
@@ -3196,29 +3092,14 @@ extern "C" int alch_ct_tunnel(const alch_tunnel* t, const alch_buf* in, alch_buf
     alch_ring* rs = t->rs;
     alch_ring* rr = t->rr;
     BIND(rs);
-    if (!rs->ev_x) HIP_TRY(hipEventCreateWithFlags(&rs->ev_x, hipEventDisableTiming));
-    if (rr->stream != rs->stream) {                       // everything runs on the target ring's stream
-        HIP_TRY(hipEventRecord(rs->ev_x, rr->stream));
-        HIP_TRY(hipStreamWaitEvent(rs->stream, rs->ev_x, 0));
-    }
     alch_ring* rin = in->ring;
-    if (rin->stream != rs->stream && rin != rr) {
-        HIP_TRY(hipEventRecord(rs->ev_x, rin->stream));
-        HIP_TRY(hipStreamWaitEvent(rs->stream, rs->ev_x, 0));
-    }
-    int rc = rs->word == 4 ? do_tunnel<u32>(t, rin, in->dptr, out->dptr, batch, s_pre, flags)
-                           : do_tunnel<u64>(t, rin, in->dptr, out->dptr, batch, s_pre, flags);
-    if (rc != ALCH_OK) return rc;
+    int rc;
+    if ((rc = ext_order(rs, rr, true)) != ALCH_OK) return rc;                       // everything runs on the target ring's stream
+    if (rin != rr && (rc = ext_order(rs, rin, true)) != ALCH_OK) return rc;
+    if ((rc = ALCH_BY_WORD(rs, do_tunnel, t, rin, in->dptr, out->dptr, batch, s_pre, flags)) != ALCH_OK) return rc;
     if (flags & ALCH_POW_OUT) if ((rc = buf_crt(out, 0, 2 * batch, true)) != ALCH_OK) return rc;
-    if (rr->stream != rs->stream) {
-        HIP_TRY(hipEventRecord(rs->ev_x, rs->stream));
-        HIP_TRY(hipStreamWaitEvent(rr->stream, rs->ev_x, 0));
-    }
-    if (rin != rr && rin->stream != rs->stream) {
-        HIP_TRY(hipEventRecord(rs->ev_x, rs->stream));
-        HIP_TRY(hipStreamWaitEvent(rin->stream, rs->ev_x, 0));
-    }
-    return ALCH_OK;
+    if ((rc = ext_order(rs, rr, false)) != ALCH_OK) return rc;
+    return rin != rr ? ext_order(rs, rin, false) : ALCH_OK;
 } catch (...) { return abi_catch(); }
 
 // ------------------------------------------------------------------------------------------------------
@@ -3233,11 +3114,7 @@ static int do_mod_switch(alch_ring* rin, alch_ring* rout, const void* in, void* 
     if (rout->L > rin->L) {                                   // up: Rescale b -> (a, b), any basis
         const int dup = rout->L - rin->L;
         uint64_t mult[MAXL] = {0};
-        for (int j = dup; j < rout->L; ++j) {
-            u64 v = 1;
-            for (int u = 0; u < dup; ++u) v = h_mulmod(v, rout->q[u] % rout->q[j], rout->q[j]);
-            mult[j] = v;
-        }
+        for (int j = dup; j < rout->L; ++j) mult[j] = up_scalar(rout, dup, j, 1);
         Scal<W> sm;
         scal_to_mont<W>(rout, mult, 1, sm);
         const size_t total = P * batch * elem_words(rout);
@@ -3251,21 +3128,16 @@ static int do_mod_switch(alch_ring* rin, alch_ring* rout, const void* in, void* 
     const size_t eb = elem_bytes(rin);
     const bool dec_c0 = per == 2 && rin->gen && rin->gh.rad > 1;
     if (rin->gen && rin->opts.rs_lin && ddn <= MAXDROP && !(flags & ALCH_POW_IN)) {
-        // kept limbs stay in the CRT basis (k_gen_rescale_drop / k_gen_rescale_keep)
-        DropTab<W> dt;
-        fill_drop_tab<W>(rin, ddn, dt);
+        // kept limbs stay in the CRT basis
         const size_t per_b = P * (size_t)ddn * n * sizeof(W);
         size_t chunk = std::min(batch, std::max<size_t>(1, (rin->scratch_mib << 20) / per_b));
         int rc = ensure_ws(&rin->ws_full, &rin->ws_full_bytes, chunk * per_b);
         if (rc != ALCH_OK) return rc;
         for (size_t done = 0; done < batch; done += chunk) {
             const size_t now = std::min(chunk, batch - done);
-            hipError_t e = gen_rescale_lin_dispatch(dev_ring<W>(rin), gen_dev<W>(rin),
-                                                    reinterpret_cast<const W*>(reinterpret_cast<const char*>(in) + done * P * eb),
-                                                    reinterpret_cast<W*>(rin->ws_full),
-                                                    reinterpret_cast<W*>(reinterpret_cast<char*>(out) + done * P * elem_bytes(rout)), dt,
-                                                    dec_c0 ? 1 : 0, P * now, rin->stream, (flags & ALCH_POW_OUT) != 0);
-            if (e != hipSuccess) return fail(ALCH_E_HIP, std::string("rescale launch: ") + hipGetErrorString(e));
+            if ((rc = rescale_down_crt<W>(rin, ddn, reinterpret_cast<const char*>(in) + done * P * eb, rin->ws_full,
+                                          reinterpret_cast<char*>(out) + done * P * elem_bytes(rout), P * now, dec_c0,
+                                          (flags & ALCH_POW_OUT) != 0)) != ALCH_OK) return rc;
         }
         return ALCH_OK;
     }
@@ -3277,13 +3149,7 @@ static int do_mod_switch(alch_ring* rin, alch_ring* rout, const void* in, void* 
     char* cur0 = reinterpret_cast<char*>(rin->ws_full);
     char* ping = cur0 + chunk * P * eb;
     char* pong = ping + chunk * P * eb;
-    auto suffix = [&](int u) {
-        DevRing<W> d = dev_ring<W>(rin);
-        d.L = L - u;
-        for (int j = 0; j + u < L; ++j) d.mod[j] = d.mod[j + u];
-        return d;
-    };
-    const size_t in_bytes = P * eb, out_bytes = P * elem_bytes(rout);
+    const size_t in_bytes = P * eb;
     for (size_t done = 0; done < batch; done += chunk) {
         const size_t now = std::min(chunk, batch - done);
         const char* src = reinterpret_cast<const char*>(in) + done * in_bytes;
@@ -3293,25 +3159,7 @@ static int do_mod_switch(alch_ring* rin, alch_ring* rout, const void* in, void* 
             HIP_TRY(hipMemcpyAsync(cur0, src, now * in_bytes, hipMemcpyDeviceToDevice, rin->stream));
             if ((rc = do_crt<W>(rin, cur0, 0, P * now, true)) != ALCH_OK) return rc;
         }
-        if (dec_c0 && (rc = do_columns<W>(rin, GEN_LINV, cur0, 0, now, 2)) != ALCH_OK) return rc;
-        char* cur = cur0;
-        for (int u = 0; u < ddn; ++u) {
-            char* nxt = (u + 1 == ddn) ? reinterpret_cast<char*>(out) + done * out_bytes : ((u & 1) ? pong : ping);
-            const DevRing<W> rs = suffix(u);
-            Scal<W> sm;
-            for (int j = 0; j < MAXL; ++j) sm.v[j] = 0;
-            const int bits = 8 * (int)sizeof(W);
-            for (int j = 1; j < rs.L; ++j) {
-                const u64 qj = rin->q[u + j];
-                sm.v[j] = (W)h_mulmod(h_powmod(rin->q[u] % qj, qj - 2, qj), h_powmod(2, (u64)bits, qj), qj);
-            }
-            const size_t total = P * now * (size_t)(rs.L - 1) * n;
-            hipLaunchKernelGGL((k_rescale_drop0<W>), dim3(ew_grid(total)), dim3(256), 0, rin->stream, rs, (const W*)cur, (W*)nxt, P * now, sm);
-            HIP_TRY(hipGetLastError());
-            cur = nxt;
-        }
-        if (dec_c0 && (rc = do_columns<W>(rout, GEN_L, out, 2 * done, now, 2, rin->stream)) != ALCH_OK) return rc;
-        if (!(flags & ALCH_POW_OUT) && (rc = do_crt<W>(rout, out, P * done, P * now, false, nullptr, rin->stream)) != ALCH_OK) return rc;
+        if ((rc = rescale_down_limbs<W>(rin, rout, cur0, ping, pong, out, done, now, P, dec_c0, (flags & ALCH_POW_OUT) != 0)) != ALCH_OK) return rc;
     }
     return ALCH_OK;
 }
@@ -3330,13 +3178,10 @@ extern "C" int alch_ct_mod_switch(const alch_buf* in, alch_buf* out, size_t batc
     alch_ring* rw = up ? rout : rin;                          // the ring whose stream carries the work
     alch_ring* ro = up ? rin : rout;
     BIND(rw);
-    if (!rw->ev_x) HIP_TRY(hipEventCreateWithFlags(&rw->ev_x, hipEventDisableTiming));
-    if (ro->stream != rw->stream) { HIP_TRY(hipEventRecord(rw->ev_x, ro->stream)); HIP_TRY(hipStreamWaitEvent(rw->stream, rw->ev_x, 0)); }
-    int rc = rin->word == 4 ? do_mod_switch<u32>(rin, rout, in->dptr, out->dptr, batch, flags)
-                            : do_mod_switch<u64>(rin, rout, in->dptr, out->dptr, batch, flags);
-    if (rc != ALCH_OK) return rc;
-    if (ro->stream != rw->stream) { HIP_TRY(hipEventRecord(rw->ev_x, rw->stream)); HIP_TRY(hipStreamWaitEvent(ro->stream, rw->ev_x, 0)); }
-    return ALCH_OK;
+    int rc;
+    if ((rc = ext_order(rw, ro, true)) != ALCH_OK) return rc;
+    if ((rc = ALCH_BY_WORD(rin, do_mod_switch, rin, rout, in->dptr, out->dptr, batch, flags)) != ALCH_OK) return rc;
+    return ext_order(rw, ro, false);
 } catch (...) { return abi_catch(); }
 
 // ------------------------------------------------------------------------------------------------------
@@ -3352,17 +3197,12 @@ extern "C" int alch_buf_rescale_drop0(const alch_buf* src, alch_buf* dst, size_t
     for (int j = 1; j < rs->L; ++j)
         if (rs->q[j] != rd->q[j - 1]) return fail(ALCH_E_INVALID, "destination limbs must equal source limbs 1..L-1");
     if (count > src->n_elems || count > dst->n_elems) return fail(ALCH_E_INVALID, "count out of bounds");
-    uint64_t inv[MAXL] = {0};
-    for (int j = 1; j < rs->L; ++j) inv[j] = h_powmod(rs->q[0] % rs->q[j], rs->q[j] - 2, rs->q[j]);
     const size_t total = count * (size_t)rd->L * rd->n;
     HIP_TRY(hipStreamSynchronize(rd->stream));
-    if (rs->word == 4) {
-        Scal<u32> sm; scal_to_mont<u32>(rs, inv, 1, sm);
-        hipLaunchKernelGGL((k_rescale_drop0<u32>), dim3(ew_grid(total)), dim3(256), 0, rs->stream, rs->d32, (const u32*)src->dptr, (u32*)dst->dptr, count, sm);
-    } else {
-        Scal<u64> sm; scal_to_mont<u64>(rs, inv, 1, sm);
-        hipLaunchKernelGGL((k_rescale_drop0<u64>), dim3(ew_grid(total)), dim3(256), 0, rs->stream, rs->d64, (const u64*)src->dptr, (u64*)dst->dptr, count, sm);
-    }
+    if (rs->word == 4)
+        hipLaunchKernelGGL((k_rescale_drop0<u32>), dim3(ew_grid(total)), dim3(256), 0, rs->stream, rs->d32, (const u32*)src->dptr, (u32*)dst->dptr, count, drop0_inv_mont<u32>(rs, 0));
+    else
+        hipLaunchKernelGGL((k_rescale_drop0<u64>), dim3(ew_grid(total)), dim3(256), 0, rs->stream, rs->d64, (const u64*)src->dptr, (u64*)dst->dptr, count, drop0_inv_mont<u64>(rs, 0));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(rs->stream));
     return ALCH_OK;

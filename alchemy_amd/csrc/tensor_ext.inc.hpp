@@ -117,15 +117,6 @@ static int ext_tables(alch_ring* small, alch_ring* big, const ExtTab** out) {
     return ALCH_OK;
 }
 
-// order dst-ring work after everything queued on src's stream, and hand back
-static int ext_order(alch_ring* work, alch_ring* other, bool before) {
-    if (work->stream == other->stream) return ALCH_OK;
-    if (!work->ev_x) HIP_TRY(hipEventCreateWithFlags(&work->ev_x, hipEventDisableTiming));
-    if (before) { HIP_TRY(hipEventRecord(work->ev_x, other->stream)); HIP_TRY(hipStreamWaitEvent(work->stream, work->ev_x, 0)); }
-    else { HIP_TRY(hipEventRecord(work->ev_x, work->stream)); HIP_TRY(hipStreamWaitEvent(other->stream, work->ev_x, 0)); }
-    return ALCH_OK;
-}
-
 template <typename W>
 static int ext_gather(alch_ring* work, const void* in, void* out, const int32_t* tab, u32 n_in, u32 n_out, u32 rows, size_t elems) {
     const size_t total = elems * rows * (size_t)work->L * n_out;
@@ -157,8 +148,7 @@ extern "C" int alch_buf_embed(alch_buf* dst, const alch_buf* src, size_t count, 
         from = s;
     }
     const int32_t* tab = basis == ALCH_BASIS_CRT ? t->slot_small : t->pow_gather;
-    rc = big->word == 4 ? ext_gather<u32>(big, from->dptr, dst->dptr, tab, small->n, big->n, 1, count)
-                        : ext_gather<u64>(big, from->dptr, dst->dptr, tab, small->n, big->n, 1, count);
+    rc = ALCH_BY_WORD(big, ext_gather, big, from->dptr, dst->dptr, tab, small->n, big->n, 1, count);
     if (rc != ALCH_OK) return rc;
     if (basis == ALCH_BASIS_DEC && big->gen && big->gh.rad > 1 && (rc = columns(big, GEN_LINV, dst->dptr, 0, count, 1)) != ALCH_OK) return rc;
     return ext_order(big, small, false);
@@ -177,8 +167,7 @@ extern "C" int alch_buf_twace(alch_buf* dst, const alch_buf* src, size_t count, 
     BIND(small);
     if ((rc = ext_order(small, big, true)) != ALCH_OK) return rc;
     if (basis != ALCH_BASIS_CRT) {                                             // twacePowDec: the same positions on either basis
-        rc = small->word == 4 ? ext_gather<u32>(small, src->dptr, dst->dptr, t->coeffs, big->n, small->n, 1, count)
-                              : ext_gather<u64>(small, src->dptr, dst->dptr, t->coeffs, big->n, small->n, 1, count);
+        rc = ALCH_BY_WORD(small, ext_gather, small, src->dptr, dst->dptr, t->coeffs, big->n, small->n, 1, count);
         if (rc != ALCH_OK) return rc;
         return ext_order(small, big, false);
     }
@@ -187,20 +176,14 @@ extern "C" int alch_buf_twace(alch_buf* dst, const alch_buf* src, size_t count, 
     for (int j = 0; j < small->L; ++j) sc[j] = h_invmod((mhb / mhs) % small->q[j], small->q[j]);
     const size_t total = count * elem_words(small);
     if (small->word == 4) {
-        GTab<u32> gb{}, gi{};
-        for (int j = 0; j < small->L; ++j) {
-            gb.p[j] = (big->gen && big->gh.rad > 1) ? big->g32.gcrt[j] : nullptr;
-            gi.p[j] = (small->gen && small->gh.rad > 1) ? small->g32.gcrt_inv[j] : nullptr;
-        }
+        GTab<u32> gb = g_table<u32>(big), gi{};
+        for (int j = 0; j < small->L; ++j) gi.p[j] = (small->gen && small->gh.rad > 1) ? small->g32.gcrt_inv[j] : nullptr;
         Scal<u32> sm; scal_to_mont<u32>(small, sc, 1, sm);
         hipLaunchKernelGGL((k_ext_twace_crt<u32>), dim3(ew_grid(total)), dim3(256), 0, small->stream, small->d32, (const u32*)src->dptr,
                            (u32*)dst->dptr, t->fibres, t->fibre, big->n, small->n, gb, gi, sm, count);
     } else {
-        GTab<u64> gb{}, gi{};
-        for (int j = 0; j < small->L; ++j) {
-            gb.p[j] = (big->gen && big->gh.rad > 1) ? big->g64.gcrt[j] : nullptr;
-            gi.p[j] = (small->gen && small->gh.rad > 1) ? small->g64.gcrt_inv[j] : nullptr;
-        }
+        GTab<u64> gb = g_table<u64>(big), gi{};
+        for (int j = 0; j < small->L; ++j) gi.p[j] = (small->gen && small->gh.rad > 1) ? small->g64.gcrt_inv[j] : nullptr;
         Scal<u64> sm; scal_to_mont<u64>(small, sc, 1, sm);
         hipLaunchKernelGGL((k_ext_twace_crt<u64>), dim3(ew_grid(total)), dim3(256), 0, small->stream, small->d64, (const u64*)src->dptr,
                            (u64*)dst->dptr, t->fibres, t->fibre, big->n, small->n, gb, gi, sm, count);
@@ -220,8 +203,7 @@ extern "C" int alch_buf_coeffs(alch_buf* dst, const alch_buf* src, size_t count)
     if (count == 0) return ALCH_OK;
     BIND(small);
     if ((rc = ext_order(small, big, true)) != ALCH_OK) return rc;
-    rc = small->word == 4 ? ext_gather<u32>(small, src->dptr, dst->dptr, t->coeffs, big->n, small->n, t->d_rel, count)
-                          : ext_gather<u64>(small, src->dptr, dst->dptr, t->coeffs, big->n, small->n, t->d_rel, count);
+    rc = ALCH_BY_WORD(small, ext_gather, small, src->dptr, dst->dptr, t->coeffs, big->n, small->n, t->d_rel, count);
     if (rc != ALCH_OK) return rc;
     return ext_order(small, big, false);
 } catch (...) { return abi_catch(); }
