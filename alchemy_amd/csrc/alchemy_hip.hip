@@ -147,6 +147,9 @@ struct alch_tunnel {
     int32_t* table_e = nullptr;                // device: [d_rel][n_e] source positions in R'
     u32* slot_e = nullptr;                     // device: [n_s] CRT slot of E' behind every CRT slot of S'
     bool pieces_ok = false;                    // every aligned group of four S' slots reads four consecutive, aligned E' slots
+    // both rings two-power with m >= 32 (the radix-16 engine): do_tunnel_pow2 -- closed-form index maps, no tables, `re` unused
+    bool pow2 = false;
+    u32 sh = 0;                                // log2(n_s / n_r) in the up direction (S' slot k reads slot k >> sh of R'), else 0
 };
 
 struct alch_hint {
@@ -229,7 +232,7 @@ static std::recursive_mutex& device_mutex(int dev) {
     } while (0)
 
 extern "C" const char* alch_last_error(void) { return g_err.c_str(); }
-extern "C" uint32_t alch_version(void) { return (1u << 16) | 6u; }   // 1.6: alch_buf_checksum_at, shared streams owned by their last user; 1.5: device-resident Tensor values (alch_buf_tensor_op, alch_buf_copy, alch_ring_share_stream, pooled small buffers, pinned staging), status order of alch_ring_create; 1.4: general cyclotomic indices, l / lInv, real mulG / divG, mulPublic / addPublic, alch_ring_set_option; 1.3: + alch_decompose_base2, BaseBGad hints, alch_ct_mul_full, alch_buf_device_ptr, n = 2^16
+extern "C" uint32_t alch_version(void) { return (1u << 16) | 7u; }   // 1.7: ring tunnels between two-power rings with m >= 32 (do_tunnel_pow2); 1.6: alch_buf_checksum_at, shared streams owned by their last user; 1.5: device-resident Tensor values (alch_buf_tensor_op, alch_buf_copy, alch_ring_share_stream, pooled small buffers, pinned staging), status order of alch_ring_create; 1.4: general cyclotomic indices, l / lInv, real mulG / divG, mulPublic / addPublic, alch_ring_set_option; 1.3: + alch_decompose_base2, BaseBGad hints, alch_ct_mul_full, alch_buf_device_ptr, n = 2^16
 
 // ------------------------------------------------------------------------------------------------------
 // element-wise kernels (HBM-bound; 16 B per lane, grid-stride, ~2048 workgroups)
@@ -905,6 +908,222 @@ __global__ void k_tunnel_lin(DevRing<W> Rs, W* out, const W* x0crt, const W* lin
         }
         *reinterpret_cast<P*>(out + 2 * ct * Ln + rem) = acc;
         *reinterpret_cast<P*>(out + (2 * ct + 1) * Ln + rem) = zero;
+    }
+}
+
+// ---- tunnels between two-power rings of the radix-16 engine (do_tunnel_pow2) ---------------------------------------------------
+// Both rings are Z_q[X]/(X^n + 1); with d = d_rel = max(1, n_r / n_s) and n_d = n_r / d (the dimension the transforms run at):
+//   coeffs     E'-coefficient i of a Pow vector over R' is its stride-d subsequence starting at i (zeta_e = X^d; g = 1, l = identity)
+//   embedCRT   crt_S'(embedPow x)[k] = crt_R'(x)[k >> sh], n_s = 2^sh n_d: the slot rule is bit-reversed, so the 2^sh slots of S'
+//              above a slot of the smaller ring are consecutive (sh = 0 in the down direction, where E' = S')
+// Step 1, the gather: from the Pow copy of (c0, c1) over R' ([ct][2][Lin][n_r], Lin = L - dup limbs: the ciphertexts may sit dup limbs
+// below the tunnel's ring, the added moduli are folded into s_m) to
+//   x0   [ct][d][Lin][n_d]        the E'-coefficients of c0 times s_m (null: not wanted -- CRT input in the up direction)
+//   dst1 TRIV:  [ct][d][Lin][L][n_d]  the TrivGad digits of the coefficients of c1 s_m: centred lift of limb i reduced into every limb
+//        !TRIV: [ct][d][L][n_d]       the coefficients of c1 s_m themselves, zero in the dup leading limbs (BaseBGad 2 decomposes later)
+// A thread owns VL consecutive positions of G = min(d, VL) neighbouring coefficients: its VL x G source words are G (d < VL) or VL
+// whole 16-byte pieces, transposed in registers, so every access is a 16-byte one.
+template <typename W, int G, bool TRIV>
+__global__ void __launch_bounds__(256) k_tun2_gather(DevRing<W> Rs, const W* in, W* x0, W* dst1, u32 d, u32 n_d, size_t nct, Scal<W> s_m, int scale,
+                                                     u32 dup, int balanced) {
+    typedef typename Vec4<W>::type V;
+    typedef typename Signed<W>::type SW;
+    constexpr int VL = Vec4<W>::LANES;
+    const u32 L = (u32)Rs.L, Lin = L - dup;
+    const u32 Lw = TRIV ? Lin : L;                               // limbs walked per component
+    const u32 c0 = x0 ? 0u : 1u, ncomp = 2u - c0;
+    const u32 nv = n_d / VL, ng = d / G;
+    const size_t n_r = (size_t)n_d * d;
+    ALCH_WALK_INIT(nv * ng, ncomp * Lw);
+    ALCH_WALK(w, nct * ncomp * Lw * ng * nv, wk) {
+        const size_t ct = wk.outer;
+        const u32 comp = wk.mid / Lw + c0, limb = wk.mid % Lw + (TRIV ? dup : 0u);
+        const u32 k4 = (wk.k % nv) * VL, i0 = (wk.k / nv) * G;
+        V t[G];                                                  // t[a][kk]: coefficient i0 + a, position k4 + kk
+        if (limb < dup) {
+#pragma unroll
+            for (int a = 0; a < G; ++a)
+#pragma unroll
+                for (int e = 0; e < VL; ++e) t[a][e] = 0;
+        } else {
+            const W* src = in + ((2 * ct + comp) * Lin + (limb - dup)) * n_r;
+            const ModP<W> m = Rs.mod[limb];
+            if constexpr (G == VL) {                             // d >= VL: one piece per position, VL coefficients wide
+#pragma unroll
+                for (int c = 0; c < VL; ++c) {
+                    const V p = *reinterpret_cast<const V*>(src + (size_t)(k4 + c) * d + i0);
+#pragma unroll
+                    for (int a = 0; a < G; ++a) t[a][c] = p[a];
+                }
+            } else {                                             // d = G < VL: the VL positions of all d coefficients are d consecutive pieces
+#pragma unroll
+                for (int c = 0; c < G; ++c) {
+                    const V p = *reinterpret_cast<const V*>(src + (size_t)k4 * G + c * VL);
+#pragma unroll
+                    for (int e = 0; e < VL; ++e) t[(c * VL + e) % G][(c * VL + e) / G] = p[e];
+                }
+            }
+            if (scale) {
+#pragma unroll
+                for (int a = 0; a < G; ++a)
+#pragma unroll
+                    for (int e = 0; e < VL; ++e) t[a][e] = mont_mul(t[a][e], s_m.v[limb], m);
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < G; ++a) {
+            const size_t ci = ct * d + i0 + a;
+            if (comp == 0) {                                     // compact: the dup leading limbs (walked for !TRIV only) have no place in x0
+                if (limb >= dup) *reinterpret_cast<V*>(x0 + (ci * Lin + (limb - dup)) * (size_t)n_d + k4) = t[a];
+            } else if (!TRIV) {
+                *reinterpret_cast<V*>(dst1 + (ci * L + limb) * (size_t)n_d + k4) = t[a];
+            } else {
+                const W qi = Rs.mod[limb].q, hq = (qi - 1) >> 1;
+                for (u32 j = 0; j < L; ++j) {
+                    const W qj = Rs.mod[j].q;
+                    V r;
+#pragma unroll
+                    for (int e = 0; e < VL; ++e) {
+                        const SW z = t[a][e] > hq ? (SW)t[a][e] - (SW)qi : (SW)t[a][e];
+                        r[e] = balanced ? (W)(z < 0 ? z + (SW)qj : z) : (W)reduce_signed<W>(z, qj);
+                    }
+                    *reinterpret_cast<V*>(dst1 + ((ci * Lin + (limb - dup)) * L + j) * (size_t)n_d + k4) = r;
+                }
+            }
+        }
+    }
+}
+
+// Step 2, the hint inner product with slot replication: for S' slot k and TILE ciphertexts sharing every hint piece,
+//   c0'[k] = sum_i x0crt_i[k >> sh] lin_i[k] + sum_d digit_d[k >> sh] hint_{d,0}[k],   c1'[k] = sum_d digit_d[k >> sh] hint_{d,1}[k]
+// (evalLin's constant term is the starting value, as in k_tunnel_mac_e).  A thread owns one 16-byte piece of S' slots; the VL digit
+// words behind it lie in ONE aligned 16-byte piece of the small vector (all VL the same word once sh >= log2 VL), which it loads whole and
+// picks from -- the lanes of a wavefront that share a piece are served by one request, so a digit word is fetched once per wavefront
+// pass, not once per replicated slot, and every access stays a 16-byte one.
+// digits: [ct][D][L][n_d], digit d uses hint row hd = d + (d / grp + 1) hskip (compact TrivGad digits of ciphertexts hskip limbs below the
+// ring; hskip = 0: hd = d).  x0: element (ct, i) limb j >= xoff at x0 + ct x0_cts + (i Lx + j - xoff) n_d; x0_scale: times s_m on the fly
+// (CRT input in the up direction, where c0 is read in place).  32-bit words: lazy 64-bit groups of K = floor((2^32 - 1) / q) - 2 products
+// per reduction, product-at-a-time where K < 2, exactly as k_tunnel_mac_e; 64-bit words: one Montgomery product at a time.
+template <typename W> __device__ __forceinline__ W tun2_pick(typename Vec4<W>::type p, u32 i);
+template <> __device__ __forceinline__ u32 tun2_pick<u32>(Vec4<u32>::type p, u32 i) { const u32 lo = (i & 1) ? p[1] : p[0], hi = (i & 1) ? p[3] : p[2]; return (i & 2) ? hi : lo; }
+template <> __device__ __forceinline__ u64 tun2_pick<u64>(Vec4<u64>::type p, u32 i) { return (i & 1) ? p[1] : p[0]; }
+
+template <typename W, int TILE>
+__global__ void __launch_bounds__(256) k_tun2_mac(DevRing<W> R, W* out, const W* digits, const W* hint, size_t nct, u32 D, u32 grp, u32 hskip, u32 sh,
+                                                  u32 n_d, const W* x0, size_t x0_cts, const W* lin, u32 d_rel, u32 Lx, u32 xoff, Scal<W> s_m,
+                                                  int x0_scale) {
+    typedef typename Vec4<W>::type V;
+    constexpr int VL = Vec4<W>::LANES;
+    const size_t n = (size_t)R.n;
+    const size_t Ln = (size_t)R.L * n;
+    const size_t ntile = (nct + TILE - 1) / TILE;
+    const size_t nv = n / VL;
+    ALCH_WALK_INIT(nv, R.L);
+    ALCH_WALK(w, ntile * (size_t)R.L * nv, wk) {
+        const size_t ct0 = wk.outer * TILE, rem = (size_t)wk.mid * n + (size_t)wk.k * VL;
+        const u32 limb = wk.mid;
+        const ModP<W> m = R.mod[limb];
+        const W q = m.q, qni = m.qni;
+        // the digit words behind this piece: word (k + e) >> sh, all inside the aligned piece that starts at `se`
+        const u32 k0 = wk.k * (u32)VL;
+        const u32 se = (k0 >> sh) & ~(u32)(VL - 1);
+        u32 pick[VL];
+#pragma unroll
+        for (int e = 0; e < VL; ++e) pick[e] = ((k0 + (u32)e) >> sh) - se;
+        auto spread = [&](V p) -> V {
+            if (sh == 0) return p;
+            V x;
+#pragma unroll
+            for (int e = 0; e < VL; ++e) x[e] = tun2_pick<W>(p, pick[e]);
+            return x;
+        };
+        bool lazy = false;
+        u32 K = 0;
+        if constexpr (sizeof(W) == 4) {
+            const u32 kmax = 0xFFFFFFFFu / (u32)q;                 // (K + 2) q < 2^32
+            K = kmax >= 4 ? (kmax - 2 > 8 ? 8u : kmax - 2) : 0u;
+            lazy = K >= 2;
+        }
+        const u64 r1 = lazy ? (u64)m.r1 : 1;                       // not lazy: the accumulators hold the running sum itself, in [0, q)
+        u64 a0[TILE][VL], a1[TILE][VL];
+        const W* dv[TILE];
+#pragma unroll
+        for (int c = 0; c < TILE; ++c) {
+            const size_t ct = ct0 + c < nct ? ct0 + c : ct0;       // a dead lane of the tile recomputes ciphertext ct0 and stores nothing
+            dv[c] = digits + (ct * (size_t)D * R.L + limb) * (size_t)n_d + se;
+#pragma unroll
+            for (int e = 0; e < VL; ++e) { a0[c][e] = 0; a1[c][e] = 0; }
+            if (limb >= xoff) {
+                for (u32 i = 0; i < d_rel; ++i) {
+                    const V x = spread(*reinterpret_cast<const V*>(x0 + ct * x0_cts + ((size_t)i * Lx + (limb - xoff)) * (size_t)n_d + se));
+                    const V y = *reinterpret_cast<const V*>(lin + (size_t)i * Ln + rem);
+#pragma unroll
+                    for (int e = 0; e < VL; ++e) {
+                        const W xs = x0_scale ? mont_mul(x[e], s_m.v[limb], m) : x[e];
+                        a0[c][e] = (u64)add_mod((W)a0[c][e], mont_mul(xs, y[e], m), q);
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < VL; ++e) a0[c][e] = a0[c][e] * r1;
+            }
+        }
+        const size_t dstep = (size_t)R.L * n_d;
+        if (lazy) {
+            if constexpr (sizeof(W) == 4) {
+                auto redc = [&](u64 t) -> u32 { const u32 mm = (u32)t * qni; return (u32)((t + (u64)mm * q) >> 32); };     // t < q 2^32 -> [0, 2q)
+                for (u32 d0 = 0; d0 < D; d0 += K) {
+                    const u32 dend = d0 + K < D ? d0 + K : D;
+                    for (u32 d = d0; d < dend; ++d) {
+                        const u32 hd = hskip ? d + (d / grp + 1) * hskip : d;
+                        const V h0 = *reinterpret_cast<const V*>(hint + (size_t)(2 * hd) * Ln + rem);
+                        const V h1 = *reinterpret_cast<const V*>(hint + (size_t)(2 * hd + 1) * Ln + rem);
+#pragma unroll
+                        for (int c = 0; c < TILE; ++c) {
+                            const V x = spread(*reinterpret_cast<const V*>(dv[c] + (size_t)d * dstep));
+#pragma unroll
+                            for (int e = 0; e < VL; ++e) {
+                                a0[c][e] += (u64)x[e] * h0[e];
+                                a1[c][e] += (u64)x[e] * h1[e];
+                            }
+                        }
+                    }
+                    if (dend < D) {                                 // carry the running sum into the next group: t (R mod q) < 2 q^2
+#pragma unroll
+                        for (int c = 0; c < TILE; ++c)
+#pragma unroll
+                            for (int e = 0; e < VL; ++e) { a0[c][e] = (u64)redc(a0[c][e]) * r1; a1[c][e] = (u64)redc(a1[c][e]) * r1; }
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < TILE; ++c)
+#pragma unroll
+                    for (int e = 0; e < VL; ++e) { a0[c][e] = csub(redc(a0[c][e]), q); a1[c][e] = csub(redc(a1[c][e]), q); }
+            }
+        } else {
+            for (u32 d = 0; d < D; ++d) {
+                const u32 hd = hskip ? d + (d / grp + 1) * hskip : d;
+                const V h0 = *reinterpret_cast<const V*>(hint + (size_t)(2 * hd) * Ln + rem);
+                const V h1 = *reinterpret_cast<const V*>(hint + (size_t)(2 * hd + 1) * Ln + rem);
+#pragma unroll
+                for (int c = 0; c < TILE; ++c) {
+                    const V x = spread(*reinterpret_cast<const V*>(dv[c] + (size_t)d * dstep));
+#pragma unroll
+                    for (int e = 0; e < VL; ++e) {
+                        a0[c][e] = (u64)add_mod((W)a0[c][e], mont_mul(x[e], h0[e], m), q);
+                        a1[c][e] = (u64)add_mod((W)a1[c][e], mont_mul(x[e], h1[e], m), q);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < TILE; ++c) {
+            if (ct0 + c >= nct) continue;
+            V r0, r1v;
+#pragma unroll
+            for (int e = 0; e < VL; ++e) { r0[e] = (W)a0[c][e]; r1v[e] = (W)a1[c][e]; }
+            *reinterpret_cast<V*>(out + 2 * (ct0 + c) * Ln + rem) = r0;
+            *reinterpret_cast<V*>(out + (2 * (ct0 + c) + 1) * Ln + rem) = r1v;
+        }
     }
 }
 
@@ -2868,6 +3087,11 @@ extern "C" int alch_ct_mul_full(const alch_hint* hint, const alch_buf* a, const 
 // ------------------------------------------------------------------------------------------------------
 extern "C" int alch_tunnel_info(const alch_ring* rr, const alch_ring* rs, uint32_t* e_prime, uint32_t* d_rel) try {
     if (!rr || !rs) return fail(ALCH_E_INVALID, "null ring");
+    if (!rr->gen && !rs->gen) {                  // two two-power indices >= 32: every such pair is a tunnel, E' is the smaller ring
+        if (e_prime) *e_prime = std::min(rr->m, rs->m);
+        if (d_rel) *d_rel = rr->m > rs->m ? rr->m / rs->m : 1u;
+        return ALCH_OK;
+    }
     u32 a = rr->m, b = rs->m;
     while (b) { const u32 t = a % b; a = b; b = t; }
     GenHost ge, gr, gs;
@@ -2894,13 +3118,35 @@ extern "C" int alch_tunnel_create(alch_ring* rr, alch_ring* rs, int gadget, cons
     if (!rr || !rs || !lin_crt || !ks_crt || !out) return fail(ALCH_E_INVALID, "null argument");
     *out = nullptr;
     if (gadget != ALCH_GAD_TRIV && gadget != ALCH_GAD_BASE2) return fail(ALCH_E_INVALID, "unknown gadget");
-    if (!rr->gen || !rs->gen || !rr->has_crt || !rs->has_crt) return fail(ALCH_E_UNSUPPORTED, "tunnelling runs on general-index rings with a CRT basis");
+    if (!rr->has_crt || !rs->has_crt) return fail(ALCH_E_UNSUPPORTED, "tunnelling runs on rings with a CRT basis");
+    if (rr->gen != rs->gen)
+        return fail(ALCH_E_UNSUPPORTED, "tunnelling between a two-power ring with m >= 32 and a general-index ring (composite m, or two-power m < 32) is not served");
     if (rr->L != rs->L || rr->word != rs->word) return fail(ALCH_E_INVALID, "both rings must have the same moduli");
     for (int j = 0; j < rr->L; ++j) if (rr->q[j] != rs->q[j]) return fail(ALCH_E_INVALID, "both rings must have the same moduli");
     if (lin_crt->ring != rs || ks_crt->ring != rs) return fail(ALCH_E_INVALID, "the linear function and the hints live in the target ring");
     u32 ep = 0, d_rel = 0;
     int rc = alch_tunnel_info(rr, rs, &ep, &d_rel);
     if (rc != ALCH_OK) return rc;
+    if (!rr->gen) {                              // two-power rings of the radix-16 engine: no index tables (do_tunnel_pow2)
+        const int digits = gadget_digits(rs, gadget);
+        const size_t nlin = d_rel, nks = (size_t)d_rel * (size_t)digits * 2;
+        if (lin_crt->n_elems < nlin || ks_crt->n_elems < nks)
+            return fail(ALCH_E_INVALID, "need d_rel linear-function values and 2 * d_rel * (gadget digits) hint elements");
+        BIND(rs);
+        alch_tunnel* t = new alch_tunnel{rr, rs, d_rel, 0, nullptr, nullptr, nullptr, gadget, digits};
+        t->pow2 = true;
+        for (u32 r = rr->n; r < rs->n; r <<= 1) ++t->sh;
+        if (hipMalloc(&t->lin, nlin * elem_bytes(rs)) != hipSuccess || hipMalloc(&t->ks, nks * elem_bytes(rs)) != hipSuccess) {
+            alch_tunnel_free(t);
+            return fail(ALCH_E_NOMEM, "hipMalloc(tunnel) failed");
+        }
+        rc = ALCH_BY_WORD(rs, tunnel_to_mont, rs, t->lin, lin_crt->dptr, nlin);
+        if (rc == ALCH_OK) rc = ALCH_BY_WORD(rs, tunnel_to_mont, rs, t->ks, ks_crt->dptr, nks);
+        if (rc != ALCH_OK) { alch_tunnel_free(t); return rc; }
+        if (hipStreamSynchronize(rs->stream) != hipSuccess) { alch_tunnel_free(t); return fail(ALCH_E_HIP, "tunnel setup failed"); }
+        *out = t;
+        return ALCH_OK;
+    }
     GenHost ge;
     gen_plan(ep, ge);
     std::vector<int32_t> tab, tab_e;
@@ -3082,6 +3328,118 @@ static int do_tunnel(const alch_tunnel* t, alch_ring* rin, const void* in, void*
     return ALCH_OK;
 }
 
+// crt / crtInv in place of `count` elements that hold only the last L - u limbs of two-power ring r ([elem][L - u][n])
+template <typename W>
+static int crt_suffix(alch_ring* r, int u, void* data, size_t count, bool inverse, hipStream_t stream) {
+    if (u == 0) return do_crt<W>(r, data, 0, count, inverse, nullptr, stream);
+    const DevRing<W> dv = suffix_view<W>(r, u);
+    NttCall<W> c{};
+    c.op = inverse ? OP_CRTINV : OP_CRT;
+    c.ring = &dv; c.stream = stream; c.data = reinterpret_cast<W*>(data);
+    c.first_poly = 0; c.npoly = count * (size_t)dv.L;
+    return launch(r, c, "crt");
+}
+
+template <typename W, bool TRIV>
+static void launch_tun2_gather(alch_ring* rs, u32 d, const W* in, W* x0, W* dst1, u32 n_d, size_t nct, const Scal<W>& sm, bool scale, u32 dup) {
+    constexpr int VL = Vec4<W>::LANES;
+    const u32 g = d < (u32)VL ? d : (u32)VL;
+    const size_t items = nct * (x0 ? 2 : 1) * (size_t)(TRIV ? rs->L - (int)dup : rs->L) * (d / g) * (n_d / VL);
+    const dim3 grid(ew_grid(items)), block(256);
+    const int bal = rs->balanced ? 1 : 0, sc = scale ? 1 : 0;
+    if (g == 1) hipLaunchKernelGGL((k_tun2_gather<W, 1, TRIV>), grid, block, 0, rs->stream, dev_ring<W>(rs), in, x0, dst1, d, n_d, nct, sm, sc, dup, bal);
+    else if (g == 2) hipLaunchKernelGGL((k_tun2_gather<W, 2, TRIV>), grid, block, 0, rs->stream, dev_ring<W>(rs), in, x0, dst1, d, n_d, nct, sm, sc, dup, bal);
+    else hipLaunchKernelGGL((k_tun2_gather<W, VL, TRIV>), grid, block, 0, rs->stream, dev_ring<W>(rs), in, x0, dst1, d, n_d, nct, sm, sc, dup, bal);
+}
+
+// SymmSHE.tunnel between two two-power rings of the radix-16 engine (m >= 32 on both sides); same contract as do_tunnel.  Two shapes:
+//   up    R' = E' inside S' (d_rel = 1): coeffs is the identity and everything is transformed at dimension n_r -- crtInv of the input,
+//         the digits' crt -- while the products with the linear function and the hints read slot k >> sh (k_tun2_mac).  CRT input: c0 is
+//         read where it lies, no gather and no transform for it.
+//   down  R' over S' = E' (d_rel = n_r / n_s): crtInv at R', the stride-d_rel gather, d_rel (1 + D) transforms at n_s, sh = 0.
+// g = 1 and l = identity on a two-power index: no lInv / l step.  The digit tail follows ks_stage's ladder for two-power rings: BaseBGad 2
+// in the transforms' loader (OP_CRT_BASE2) or, on split rings, k_decompose_base2 + do_crt; TrivGad digits leave the gather already
+// decomposed and reduced (compact: only the L - dup limbs the input has) and take one batched crt.
+template <typename W>
+static int do_tunnel_pow2(const alch_tunnel* t, alch_ring* rin, const void* in, void* out, size_t batch, const uint64_t* s_pre, unsigned flags) {
+    alch_ring* rr = t->rr;
+    alch_ring* rs = t->rs;
+    const int L = rs->L, dup = rr->L - rin->L, Lin = L - dup;
+    const u32 d = t->d_rel;
+    const bool base2 = t->gadget == ALCH_GAD_BASE2, up = rs->n > rr->n, pin = (flags & ALCH_POW_IN) != 0;
+    alch_ring* rd = up ? rr : rs;                      // the ring whose dimension the transforms run at
+    const u32 n_d = rd->n;
+    const bool c0_in_place = up && !pin;               // crt_S'(embed c0)[k] = crt_R'(c0)[k >> sh]: the input's CRT form serves as it is
+    const u32 GD = base2 ? (u32)t->digits : (u32)Lin;  // digits per E'-coefficient
+    Scal<u32> b2first, b2kd;
+    if (base2) base2_layout(rs, b2first, b2kd);
+    const size_t wb = sizeof(W), ebr = elem_bytes(rin), pd = (size_t)n_d * wb;        // pd: one limb-polynomial at the transforms' dimension
+    const size_t x0_b = c0_in_place ? 0 : (size_t)d * Lin * pd, x1_b = base2 ? (size_t)d * L * pd : 0, dig_b = (size_t)d * GD * L * pd;
+    const size_t per_ct = 2 * ebr + x0_b + x1_b + dig_b;
+    size_t chunk = std::max<size_t>(1, (rs->scratch_mib << 20) / per_ct);
+    chunk = std::min(chunk, batch);
+    int rc = ensure_ws(&rs->ws_full, &rs->ws_full_bytes, chunk * per_ct);
+    if (rc != ALCH_OK) return rc;
+    char* win = reinterpret_cast<char*>(rs->ws_full);
+    char* x0 = win + chunk * 2 * ebr;
+    char* x1 = x0 + chunk * x0_b;
+    char* dig = x1 + chunk * x1_b;
+    uint64_t s_eff[MAXL] = {0};
+    for (int j = dup; j < L; ++j) s_eff[j] = up_scalar(rs, dup, j, s_pre ? s_pre[j] : 1);      // modSwitch up: times the added moduli
+    const bool scale = s_pre != nullptr || dup > 0;
+    Scal<W> sm;
+    scal_to_mont<W>(rs, s_eff, 1, sm);
+    const size_t ebs = elem_bytes(rs);
+    for (size_t done = 0; done < batch; done += chunk) {
+        const size_t now = std::min(chunk, batch - done);
+        const char* src = reinterpret_cast<const char*>(in) + done * 2 * ebr;
+        // Pow basis of R' (a copy: the caller's ciphertexts are left alone); Pow-basis input is read in place
+        if (!pin) {
+            if (split_ring(rin)) {                     // the split transforms work in place only
+                HIP_TRY(hipMemcpyAsync(win, src, now * 2 * ebr, hipMemcpyDeviceToDevice, rs->stream));
+                if ((rc = do_crt<W>(rin, win, 0, 2 * now, true, nullptr, rs->stream)) != ALCH_OK) return rc;
+            } else if ((rc = do_crt<W>(rin, win, 0, 2 * now, true, src, rs->stream)) != ALCH_OK) return rc;
+        }
+        const W* pow_in = reinterpret_cast<const W*>(pin ? src : win);
+        W* px0 = c0_in_place ? nullptr : reinterpret_cast<W*>(x0);
+        if (base2) launch_tun2_gather<W, false>(rs, d, pow_in, px0, reinterpret_cast<W*>(x1), n_d, now, sm, scale, (u32)dup);
+        else launch_tun2_gather<W, true>(rs, d, pow_in, px0, reinterpret_cast<W*>(dig), n_d, now, sm, scale, (u32)dup);
+        HIP_TRY(hipGetLastError());
+        // constant term: crt of the E'-coefficients of c0 (evalLin itself is the inner product's starting value)
+        if (px0 && (rc = crt_suffix<W>(rd, dup, x0, now * d, false, rs->stream)) != ALCH_OK) return rc;
+        // linear term: the digits' crt
+        if (base2 && !split_ring(rd)) {                // decompose + reduce in the transforms' loader
+            NttCall<W> nc{};
+            nc.op = OP_CRT_BASE2; nc.ring = &dev_ring<W>(rd); nc.stream = rs->stream; nc.balanced = rd->balanced;
+            nc.src = reinterpret_cast<const W*>(x1); nc.data = reinterpret_cast<W*>(dig);
+            nc.npoly = now * (size_t)d * GD * (size_t)L;
+            nc.b2_first = b2first; nc.b2_kd = b2kd; nc.b2_D = GD;
+            if ((rc = launch(rd, nc, "tunnel crt_base2")) != ALCH_OK) return rc;
+        } else {
+            if (base2) {
+                const size_t elems = now * d;
+                for (size_t y0 = 0; y0 < elems; y0 += 32768) {             // grid.y is 16-bit
+                    const unsigned ny = (unsigned)std::min<size_t>(32768, elems - y0);
+                    hipLaunchKernelGGL((k_decompose_base2<W>), dim3(ew_grid(elem_words(rd)), ny), dim3(256), 0, rs->stream, dev_ring<W>(rd),
+                                       reinterpret_cast<const W*>(x1) + y0 * elem_words(rd), reinterpret_cast<W*>(dig) + y0 * GD * elem_words(rd),
+                                       b2first, b2kd, GD);
+                    HIP_TRY(hipGetLastError());
+                }
+            }
+            if ((rc = do_crt<W>(rd, dig, 0, now * d * GD, false, nullptr, rs->stream)) != ALCH_OK) return rc;
+        }
+        W* po = reinterpret_cast<W*>(reinterpret_cast<char*>(out) + done * 2 * ebs);
+        const size_t pieces = (now + 3) / 4 * (size_t)L * (rs->n / Vec4<W>::LANES);
+        const W* mx0 = c0_in_place ? reinterpret_cast<const W*>(src) : reinterpret_cast<const W*>(x0);
+        const size_t x0_cts = c0_in_place ? 2 * (size_t)Lin * rr->n : (size_t)d * Lin * n_d;
+        hipLaunchKernelGGL((k_tun2_mac<W, 4>), dim3(ew_grid(pieces)), dim3(256), 0, rs->stream, dev_ring<W>(rs), po, reinterpret_cast<const W*>(dig),
+                           reinterpret_cast<const W*>(t->ks), now, d * GD, (u32)Lin, (!base2 && dup > 0) ? (u32)dup : 0u, t->sh, n_d, mx0, x0_cts,
+                           reinterpret_cast<const W*>(t->lin), d, (u32)Lin, (u32)dup, sm, (c0_in_place && scale) ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+    }
+    return ALCH_OK;
+}
+
 extern "C" int alch_ct_tunnel(const alch_tunnel* t, const alch_buf* in, alch_buf* out, size_t batch, const uint64_t* s_pre, unsigned flags) try {
     if (!t || !in || !out) return fail(ALCH_E_INVALID, "null argument");
     if ((in->ring != t->rr && !is_suffix_ring(in->ring, t->rr)) || out->ring != t->rs)
@@ -3096,7 +3454,9 @@ extern "C" int alch_ct_tunnel(const alch_tunnel* t, const alch_buf* in, alch_buf
     int rc;
     if ((rc = ext_order(rs, rr, true)) != ALCH_OK) return rc;                       // everything runs on the target ring's stream
     if (rin != rr && (rc = ext_order(rs, rin, true)) != ALCH_OK) return rc;
-    if ((rc = ALCH_BY_WORD(rs, do_tunnel, t, rin, in->dptr, out->dptr, batch, s_pre, flags)) != ALCH_OK) return rc;
+    if (t->pow2) rc = ALCH_BY_WORD(rs, do_tunnel_pow2, t, rin, in->dptr, out->dptr, batch, s_pre, flags);
+    else rc = ALCH_BY_WORD(rs, do_tunnel, t, rin, in->dptr, out->dptr, batch, s_pre, flags);
+    if (rc != ALCH_OK) return rc;
     if (flags & ALCH_POW_OUT) if ((rc = buf_crt(out, 0, 2 * batch, true)) != ALCH_OK) return rc;
     if ((rc = ext_order(rs, rr, false)) != ALCH_OK) return rc;
     return rin != rr ? ext_order(rs, rin, false) : ALCH_OK;

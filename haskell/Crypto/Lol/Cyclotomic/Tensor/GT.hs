@@ -511,6 +511,8 @@ mulFullGT hint a b out batch spre =
 -- 'c_ctTunnel' call.  PT2CT emits @modSwitch_ .: tunnel_ hint .: modSwitch_@ (PT2CT.hs:224-229): when the input buffer's ring holds
 -- only the last limbs of the tunnel's R' ring, the leading @modSwitch@ is part of this call (the added limbs are zero and skipped).
 -- Arguments: tunnel handle, input buffer (2*batch CRT-basis elements over R'), output buffer (over S'), batch, toMSD's per-limb scalar.
+-- R' and S' are two general-index rings or two two-power rings with index >= 32 (since library version 1.7; a mixed pair is
+-- @ALCH_E_UNSUPPORTED@ at @alch_tunnel_create@ and stays on the host).
 tunnelGT :: Ptr AlchTunnel -> Ptr AlchBuf -> Ptr AlchBuf -> Int -> [Word64] -> IO ()
 tunnelGT t a out batch spre =
   withArray spre $ \ps -> c_ctTunnel t a out (fromIntegral batch) ps 0 >>= check "alch_ct_tunnel"

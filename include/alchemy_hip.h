@@ -81,7 +81,7 @@ typedef struct alch_tunnel alch_tunnel;
 #define ALCH_GAD_BASE2 1           /* BaseBGad 2: sum_i ceil(log2 q_i) digits; unfused device path */
 
 const char *alch_last_error(void);
-/* Library/ABI version: (major<<16)|minor. */
+/* Library/ABI version: (major<<16)|minor; the minor number goes up with every added capability (1.7: tunnels between two-power rings). */
 uint32_t alch_version(void);
 
 /* ---- ring context ------------------------------------------------------------------------------
@@ -388,7 +388,21 @@ int alch_ct_mul_full(const alch_hint *hint, const alch_buf *a, const alch_buf *b
  * `in` may also belong to a ring holding only the LAST limbs of ring_r (same index): PT2CT emits
  * modSwitch_ .: tunnel_ hint .: modSwitch_ (PT2CT.hs:224-229) and the leading modSwitch up, x -> (0, q_a x), is then part of
  * this call -- the added limbs are zero, so their transforms, digits and hint products are skipped (same results as
- * alch_ct_mod_switch followed by alch_ct_tunnel; s_pre is indexed by ring_s's limbs either way). */
+ * alch_ct_mod_switch followed by alch_ct_tunnel; s_pre is indexed by ring_s's limbs either way).
+ * TWO-POWER RINGS (since 1.7).  The same three entry points, with the same contract word for word (lin_crt, ks_crt order i, t, (b, a),
+ * both gadgets, both word sizes, input on ring_r or on its last limbs, ALCH_POW_IN / ALCH_POW_OUT, input untouched, ring_s's stream),
+ * serve a pair of two-power rings that are BOTH on the radix-16 engine (32 <= m; every size alch_ring_create accepts, the split sizes
+ * included).  Every such pair is a tunnel; E' is the smaller ring.  Two shapes:
+ *   up    r' | s' (r' = s' counts as down): R' = E' inside S', d_rel = 1, `coeffs` is the identity.  By the embedCRT rule and the bit-reversed
+ *         slot order, crt_S'(embedPow x)[k] = crt_R'(x)[k >> sh] with n_s = 2^sh n_r: every transform runs at dimension n_r and the
+ *         products with lin_crt / ks_crt read slot k >> sh; with CRT input c0 is not transformed at all.
+ *   down  s' | r': S' = E', d_rel = n_r / n_s; E'-coefficient i of a Pow-basis element is the stride-d_rel subsequence of its coefficient
+ *         vector that starts at i.  One crtInv at R', then d_rel (1 + D) transforms at n_s.
+ * g = 1 and l = identity on a two-power index, so there is no lInv / l step.  The index maps are closed forms: no tables are built, and
+ * the ring options "tunnel_ep", "tunnel_fused" and "tunnel_mac" are read by the general-index path only ("scratch_mib" applies to both).
+ * NOT served: a pair with one ring on the radix-16 engine and the other on the general engine (a two-power partner below 32, or a
+ * composite partner): alch_tunnel_create returns ALCH_E_UNSUPPORTED and says so.  Two rings of the general engine (two-power indices
+ * below 32 among them) run the general-index path as before. */
 int alch_tunnel_info(const alch_ring *ring_r, const alch_ring *ring_s, uint32_t *e_prime, uint32_t *d_rel);
 int alch_tunnel_create(alch_ring *ring_r, alch_ring *ring_s, int gadget, const alch_buf *lin_crt, const alch_buf *ks_crt,
                        alch_tunnel **out);
