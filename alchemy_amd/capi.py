@@ -36,6 +36,7 @@ SYMBOLS = [
     "alch_buf_embed", "alch_buf_twace", "alch_buf_coeffs", "alch_embed_pow", "alch_embed_dec", "alch_embed_crt",
     "alch_twace_pow_dec", "alch_twace_crt", "alch_coeffs", "alch_ext_table", "alch_crt_set_dec", "alch_ct_add_public",
     "alch_ring_share_stream", "alch_buf_copy", "alch_buf_tensor_op", "alch_buf_view", "alch_buf_ring", "alch_ring_device",
+    "alch_ct_error_term", "alch_buf_lift", "alch_ct_decrypt_lift",
 ]
 
 
@@ -156,6 +157,9 @@ def load_library():
         "alch_twace_pow_dec": [VP, VP, P64, P64], "alch_twace_crt": [VP, VP, P64, P64], "alch_coeffs": [VP, VP, P64, P64],
         "alch_ext_table": [C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)],
         "alch_crt_set_dec": [C.c_uint32, C.c_uint32, C.c_uint32, P64, C.POINTER(C.c_size_t)],
+        "alch_ct_error_term": [VP, C.c_size_t, C.c_int, VP, C.c_size_t, PU64, VP, C.c_size_t, C.c_uint],
+        "alch_buf_lift": [VP, C.c_size_t, C.c_size_t, VP, C.c_size_t, C.c_uint64, PU64],
+        "alch_ct_decrypt_lift": [VP, C.c_size_t, C.c_int, VP, C.c_size_t, PU64, VP, C.c_size_t, C.c_uint64, PU64, C.c_uint],
     }
     for name, args in sig.items():
         fn = getattr(l, name)

@@ -83,6 +83,10 @@ struct alch_ring {
     void* ws_full = nullptr;                   // ct_mul_full scratch: per pipeline digits + key-switched chunk + stash
     size_t ws_full_bytes = 0;
     hipEvent_t ev_x = nullptr;                 // cross-ring ordering (ext_order)
+    void* ws_lift = nullptr;                   // decrypt / error-rate scratch: c(s) of one chunk (+ its crt'd inputs with ALCH_POW_IN)
+    size_t ws_lift_bytes = 0;
+    void* ws_maxd = nullptr;                   // digit vectors of max |lift|, 8 L bytes per element
+    size_t ws_maxd_bytes = 0;
     int device = 0;                            // HIP device the ring's streams, tables and buffers live on
     LaunchOpts opts;                           // launch-structure options (alch_ring_set_option)
     bool one_stream = false;
@@ -232,7 +236,7 @@ static std::recursive_mutex& device_mutex(int dev) {
     } while (0)
 
 extern "C" const char* alch_last_error(void) { return g_err.c_str(); }
-extern "C" uint32_t alch_version(void) { return (1u << 16) | 7u; }   // 1.7: ring tunnels between two-power rings with m >= 32 (do_tunnel_pow2); 1.6: alch_buf_checksum_at, shared streams owned by their last user; 1.5: device-resident Tensor values (alch_buf_tensor_op, alch_buf_copy, alch_ring_share_stream, pooled small buffers, pinned staging), status order of alch_ring_create; 1.4: general cyclotomic indices, l / lInv, real mulG / divG, mulPublic / addPublic, alch_ring_set_option; 1.3: + alch_decompose_base2, BaseBGad hints, alch_ct_mul_full, alch_buf_device_ptr, n = 2^16
+extern "C" uint32_t alch_version(void) { return (1u << 16) | 8u; }   // 1.8: decrypt / errorRate_ on resident batches (alch_ct_error_term, alch_buf_lift, alch_ct_decrypt_lift; kernel_lift.hpp); 1.7: ring tunnels between two-power rings with m >= 32 (do_tunnel_pow2); 1.6: alch_buf_checksum_at, shared streams owned by their last user; 1.5: device-resident Tensor values (alch_buf_tensor_op, alch_buf_copy, alch_ring_share_stream, pooled small buffers, pinned staging), status order of alch_ring_create; 1.4: general cyclotomic indices, l / lInv, real mulG / divG, mulPublic / addPublic, alch_ring_set_option; 1.3: + alch_decompose_base2, BaseBGad hints, alch_ct_mul_full, alch_buf_device_ptr, n = 2^16
 
 // ------------------------------------------------------------------------------------------------------
 // element-wise kernels (HBM-bound; 16 B per lane, grid-stride, ~2048 workgroups)
@@ -1147,6 +1151,8 @@ __global__ void k_checksum(const W* data, size_t words, u64* sum, u64 w0) {
     if ((threadIdx.x & 63) == 0) atomicAdd((unsigned long long*)sum, (unsigned long long)acc);
 }
 
+#include "kernel_lift.hpp"
+
 static inline unsigned ew_grid(size_t items) {
     size_t g = (items + 255) / 256;
     if (g > 2048) g = 2048;
@@ -1487,6 +1493,8 @@ extern "C" int alch_ring_destroy(alch_ring* r) try {
     if (r->ws_digits) (void)hipFree(r->ws_digits);
     if (r->ws_in) (void)hipFree(r->ws_in);
     if (r->ws_full) (void)hipFree(r->ws_full);
+    if (r->ws_lift) (void)hipFree(r->ws_lift);
+    if (r->ws_maxd) (void)hipFree(r->ws_maxd);
     if (r->ev_x) (void)hipEventDestroy(r->ev_x);
     if (r->ws_host) (void)hipFree(r->ws_host);
     if (r->ws_sum) (void)hipFree(r->ws_sum);
@@ -3592,6 +3600,211 @@ extern "C" int alch_buf_rescale_add0(const alch_buf* src, alch_buf* dst, size_t 
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(rd->stream));
     return ALCH_OK;
+} catch (...) { return abi_catch(); }
+
+// ------------------------------------------------------------------------------------------------------
+// decrypt and errorRate_ on resident batches (PT2CT.hs:91-99, Eval.hs:150-160): c(s) on the decoding basis, centred lift
+// ------------------------------------------------------------------------------------------------------
+static bool bytes_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const char *x = reinterpret_cast<const char*>(a), *y = reinterpret_cast<const char*>(b);
+    return x < y + nb && y < x + na;
+}
+
+// Everything alch_buf_lift's kernel needs about (source ring, destination modulus).  rd == null: no residues wanted.
+template <typename W>
+static LiftPar<W> lift_par(const alch_ring* r, const alch_ring* rd, uint64_t l_scalar) {
+    LiftPar<W> P;
+    memset(&P, 0, sizeof P);
+    const int bits = 8 * (int)sizeof(W);
+    P.L = (u32)r->L; P.n = r->n; P.bal = r->balanced ? 1u : 0u;
+    P.epw = r->n <= 128 ? 4u : 1u;                                    // up to two coefficients per lane: a wave per element
+    for (int j = 0; j < r->L; ++j) {
+        P.mod[j] = dev_ring<W>(r).mod[j];
+        const u64 qj = r->q[j], r1 = h_powmod(2, (u64)bits, qj);
+        for (int i = 0; i < j; ++i) P.inv_m[j][i] = (W)h_mulmod(h_invmod(r->q[i] % qj, qj), r1, qj);
+    }
+    const u64 p = rd ? rd->q[0] : 2;
+    u64 Qp = 1 % p;
+    for (int j = 0; j < r->L; ++j) { P.qp[j] = (u32)(r->q[j] % p); Qp = Qp * (r->q[j] % p) % p; }
+    P.p = (u32)p; P.Qp = (u32)Qp; P.lmul = (u32)(l_scalar % p); P.pinv = ~(u64)0 / p;
+    return P;
+}
+
+// Queue the lift of `count` elements at src on r's stream.  dst: 32-bit words of the Z_p ring (or null), maxd: device digits (or null).
+template <typename W>
+static int launch_lift(alch_ring* r, const alch_ring* rd, const void* src, void* dst, u64* maxd, size_t count, uint64_t l_scalar) {
+    if (count == 0 || (!dst && !maxd)) return ALCH_OK;
+    const LiftPar<W> P = lift_par<W>(r, dst ? rd : nullptr, l_scalar);
+    const size_t per = (size_t)r->L * r->n;
+    for (size_t done = 0; done < count;) {                             // grids are 32-bit
+        const size_t now = std::min<size_t>(count - done, (size_t)1 << 30);
+        hipLaunchKernelGGL((k_lift<W>), dim3((unsigned)((now + P.epw - 1) / P.epw)), dim3(256), 0, r->stream, P,
+                           reinterpret_cast<const W*>(src) + done * per, dst ? reinterpret_cast<u32*>(dst) + done * r->n : nullptr,
+                           maxd ? maxd + done * (size_t)r->L : nullptr, now);
+        done += now;
+    }
+    HIP_TRY(hipGetLastError());
+    return ALCH_OK;
+}
+
+// c(s) of `count` ciphertexts at `in` (CRT basis) into `out`, left on the decoding basis: Horner, crtInv, lInv on a general index.
+template <typename W>
+static int eval_sk_dec(alch_ring* r, const void* in, size_t count, int degree, const void* sk, const uint64_t* s_pre, void* out) {
+    Scal<W> s1, s2;
+    scal_to_mont<W>(r, s_pre, 1, s1);
+    scal_to_mont<W>(r, s_pre, 2, s2);
+    const DevRing<W>& R = dev_ring<W>(r);
+    constexpr int VL = Vec4<W>::LANES;
+    const size_t words = count * elem_words(r);
+    W* o = reinterpret_cast<W*>(out);
+    const W *i = reinterpret_cast<const W*>(in), *s = reinterpret_cast<const W*>(sk);
+    if (r->n % VL == 0) {
+        if (degree == 1) hipLaunchKernelGGL((k_ct_eval_sk<W, VL, 1>), dim3(ew_grid(words / VL)), dim3(256), 0, r->stream, R, o, i, s, words, s1, s2);
+        else hipLaunchKernelGGL((k_ct_eval_sk<W, VL, 2>), dim3(ew_grid(words / VL)), dim3(256), 0, r->stream, R, o, i, s, words, s1, s2);
+    } else {
+        if (degree == 1) hipLaunchKernelGGL((k_ct_eval_sk<W, 1, 1>), dim3(ew_grid(words)), dim3(256), 0, r->stream, R, o, i, s, words, s1, s2);
+        else hipLaunchKernelGGL((k_ct_eval_sk<W, 1, 2>), dim3(ew_grid(words)), dim3(256), 0, r->stream, R, o, i, s, words, s1, s2);
+    }
+    HIP_TRY(hipGetLastError());
+    if (int rc = do_crt<W>(r, out, 0, count, true)) return rc;
+    if (r->gen && r->gh.rad > 1) return do_columns<W>(r, GEN_LINV, out, 0, count, 1);
+    return ALCH_OK;
+}
+
+// The common body: for chunks of the batch, (crt of a copy of the input with ALCH_POW_IN,) c(s) on the decoding basis into `out` or
+// into the ring's scratch, then the lift.  out == null: decrypt_lift; dst == null && maxd == null: error_term.
+template <typename W>
+static int do_decrypt(alch_ring* r, const void* in, size_t batch, int degree, const void* sk, const uint64_t* s_pre, void* out,
+                      const alch_ring* rd, void* dst, uint64_t l_scalar, u64* maxd, bool pow_in) {
+    const size_t per = (size_t)degree + 1, eb = elem_bytes(r);
+    const size_t units = (out ? 0 : 1) + (pow_in ? per : 0);          // scratch elements per ciphertext
+    size_t chunk = batch;
+    if (units) {
+        chunk = std::max<size_t>(1, std::min<size_t>(batch, ((size_t)1 << 30) / (units * eb)));
+        if (int rc = ensure_ws(&r->ws_lift, &r->ws_lift_bytes, chunk * units * eb)) return rc;
+    }
+    char* ws_in = reinterpret_cast<char*>(r->ws_lift) + (out ? 0 : chunk * eb);
+    for (size_t done = 0; done < batch; done += chunk) {
+        const size_t now = std::min(chunk, batch - done);
+        const char* src = reinterpret_cast<const char*>(in) + done * per * eb;
+        if (pow_in) {
+            HIP_TRY(hipMemcpyAsync(ws_in, src, now * per * eb, hipMemcpyDeviceToDevice, r->stream));
+            if (int rc = do_crt<W>(r, ws_in, 0, now * per, false)) return rc;
+            src = ws_in;
+        }
+        void* cs = out ? reinterpret_cast<char*>(out) + done * eb : r->ws_lift;
+        if (int rc = eval_sk_dec<W>(r, src, now, degree, sk, s_pre, cs)) return rc;
+        if (int rc = launch_lift<W>(r, rd, cs, dst ? reinterpret_cast<char*>(dst) + done * (size_t)r->n * 4 : nullptr,
+                                    maxd ? maxd + done * (size_t)r->L : nullptr, now, l_scalar)) return rc;
+    }
+    return ALCH_OK;
+}
+
+// Argument checks shared by alch_ct_error_term and alch_ct_decrypt_lift.
+static int check_ct_sk(const char* who, const alch_buf* in, size_t batch, int degree, const alch_buf* sk, size_t sk_index, unsigned flags) {
+    const std::string w(who);
+    if (in->ring != sk->ring) return fail(ALCH_E_INVALID, w + ": the key belongs to another ring than the ciphertexts");
+    if (degree != 1 && degree != 2) return fail(ALCH_E_INVALID, w + ": degree must be 1 or 2");
+    if (flags & ~(unsigned)ALCH_POW_IN) return fail(ALCH_E_INVALID, w + ": only ALCH_POW_IN is accepted");
+    if (batch > in->n_elems / (size_t)(degree + 1)) return fail(ALCH_E_INVALID, w + ": the buffer must hold (degree + 1) * batch ring elements");
+    if (sk_index >= sk->n_elems) return fail(ALCH_E_INVALID, w + ": key index out of bounds");
+    if (!in->ring->has_crt) return fail(ALCH_E_NO_CRT, w + ": this ring has no CRT basis (created with alch_ring_create_nocrt)");
+    return ALCH_OK;
+}
+
+// The destination of a lift: one modulus 2 <= p < 2^31 over the source's index.
+static int check_lift_dst(const char* who, const alch_ring* r, const alch_buf* dst, size_t dst_first, size_t count) {
+    const std::string w(who);
+    const alch_ring* rd = dst->ring;
+    if (rd->m != r->m || rd->n != r->n) return fail(ALCH_E_INVALID, w + ": the destination ring must have the source's cyclotomic index");
+    if (rd->L != 1) return fail(ALCH_E_INVALID, w + ": the destination ring must have exactly one modulus");
+    if (rd->zdom || rd->q[0] == 0) return fail(ALCH_E_UNSUPPORTED, w + ": a lift to the integers (q = 0) is not served; lift modulo p");
+    if (rd->word != 4 || rd->q[0] >= ((u64)1 << 31)) return fail(ALCH_E_UNSUPPORTED, w + ": the destination modulus must be below 2^31");
+    if (rd->device != r->device) return fail(ALCH_E_INVALID, w + ": the rings live on different devices");
+    if (!range_ok(dst_first, count, dst->n_elems)) return fail(ALCH_E_INVALID, w + ": destination range out of bounds");
+    return ALCH_OK;
+}
+
+// Device digits for `count` elements (null when not wanted) / their download into the caller's array.
+static int maxd_get(alch_ring* r, const uint64_t* want, size_t count, u64** dev) {
+    *dev = nullptr;
+    if (!want) return ALCH_OK;
+    if (int rc = ensure_ws(&r->ws_maxd, &r->ws_maxd_bytes, count * (size_t)r->L * sizeof(u64))) return rc;
+    *dev = reinterpret_cast<u64*>(r->ws_maxd);
+    return ALCH_OK;
+}
+static int maxd_fetch(alch_ring* r, uint64_t* host, size_t count) {
+    if (!host) return ALCH_OK;
+    HIP_TRY(hipMemcpyAsync(host, r->ws_maxd, count * (size_t)r->L * sizeof(u64), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    return ALCH_OK;
+}
+
+extern "C" int alch_ct_error_term(const alch_buf* in, size_t batch, int degree, const alch_buf* sk_crt, size_t sk_index,
+                                  const uint64_t* s_pre, alch_buf* out, size_t out_first, unsigned flags) try {
+    if (!in || !sk_crt || !out) return fail(ALCH_E_INVALID, "alch_ct_error_term: null buffer");
+    alch_ring* r = in->ring;
+    BIND(r);
+    if (out->ring != r) return fail(ALCH_E_INVALID, "alch_ct_error_term: the output belongs to another ring than the ciphertexts");
+    if (int rc = check_ct_sk("alch_ct_error_term", in, batch, degree, sk_crt, sk_index, flags)) return rc;
+    if (!range_ok(out_first, batch, out->n_elems)) return fail(ALCH_E_INVALID, "alch_ct_error_term: output range out of bounds");
+    if (batch == 0) return ALCH_OK;
+    const size_t eb = elem_bytes(r);
+    void* o = reinterpret_cast<char*>(out->dptr) + out_first * eb;
+    const void* sk = reinterpret_cast<const char*>(sk_crt->dptr) + sk_index * eb;
+    if (bytes_overlap(o, batch * eb, in->dptr, batch * (size_t)(degree + 1) * eb) || bytes_overlap(o, batch * eb, sk, eb))
+        return fail(ALCH_E_INVALID, "alch_ct_error_term: the output range overlaps an input");
+    return ALCH_BY_WORD(r, do_decrypt, r, in->dptr, batch, degree, sk, s_pre, o, nullptr, nullptr, 1, nullptr, (flags & ALCH_POW_IN) != 0);
+} catch (...) { return abi_catch(); }
+
+extern "C" int alch_buf_lift(const alch_buf* src, size_t first, size_t count, alch_buf* dst_zp, size_t dst_first, uint64_t l_scalar,
+                             uint64_t* max_digits) try {
+    if (!src) return fail(ALCH_E_INVALID, "alch_buf_lift: null buffer");
+    alch_ring* r = src->ring;
+    BIND(r);
+    if (!range_ok(first, count, src->n_elems)) return fail(ALCH_E_INVALID, "alch_buf_lift: element range out of bounds");
+    if (r->zdom) return fail(ALCH_E_INVALID, "alch_buf_lift: the source is an integer ring already");
+    if (!r->has_crt) return fail(ALCH_E_UNSUPPORTED, "alch_buf_lift: the source ring needs prime moduli (a ring created with alch_ring_create)");
+    if (dst_zp) if (int rc = check_lift_dst("alch_buf_lift", r, dst_zp, dst_first, count)) return rc;
+    if (count == 0 || (!dst_zp && !max_digits)) return ALCH_OK;
+    const char* s = reinterpret_cast<const char*>(src->dptr) + first * elem_bytes(r);
+    char* d = dst_zp ? reinterpret_cast<char*>(dst_zp->dptr) + dst_first * elem_bytes(dst_zp->ring) : nullptr;
+    // the same ring lifting into itself (one limb): in place is fine -- a lane reads its coefficient before it writes it -- shifted is not
+    if (d && d != s && bytes_overlap(d, count * elem_bytes(dst_zp->ring), s, count * elem_bytes(r)))
+        return fail(ALCH_E_INVALID, "alch_buf_lift: overlapping ranges");
+    u64* maxd = nullptr;
+    int rc;
+    if ((rc = maxd_get(r, max_digits, count, &maxd)) != ALCH_OK) return rc;
+    alch_ring* rd = dst_zp ? dst_zp->ring : nullptr;
+    if (rd && (rc = ext_order(r, rd, true)) != ALCH_OK) return rc;
+    if ((rc = ALCH_BY_WORD(r, launch_lift, r, rd, s, d, maxd, count, l_scalar)) != ALCH_OK) return rc;
+    if (rd && (rc = ext_order(r, rd, false)) != ALCH_OK) return rc;
+    return maxd_fetch(r, max_digits, count);
+} catch (...) { return abi_catch(); }
+
+extern "C" int alch_ct_decrypt_lift(const alch_buf* in, size_t batch, int degree, const alch_buf* sk_crt, size_t sk_index,
+                                    const uint64_t* s_pre, alch_buf* dst_zp, size_t dst_first, uint64_t l_scalar, uint64_t* max_digits,
+                                    unsigned flags) try {
+    if (!in || !sk_crt) return fail(ALCH_E_INVALID, "alch_ct_decrypt_lift: null buffer");
+    alch_ring* r = in->ring;
+    BIND(r);
+    if (int rc = check_ct_sk("alch_ct_decrypt_lift", in, batch, degree, sk_crt, sk_index, flags)) return rc;
+    if (dst_zp) if (int rc = check_lift_dst("alch_ct_decrypt_lift", r, dst_zp, dst_first, batch)) return rc;
+    if (batch == 0 || (!dst_zp && !max_digits)) return ALCH_OK;
+    const void* sk = reinterpret_cast<const char*>(sk_crt->dptr) + sk_index * elem_bytes(r);
+    char* d = dst_zp ? reinterpret_cast<char*>(dst_zp->dptr) + dst_first * elem_bytes(dst_zp->ring) : nullptr;
+    if (d && (bytes_overlap(d, batch * elem_bytes(dst_zp->ring), in->dptr, batch * (size_t)(degree + 1) * elem_bytes(r)) ||
+              bytes_overlap(d, batch * elem_bytes(dst_zp->ring), sk, elem_bytes(r))))
+        return fail(ALCH_E_INVALID, "alch_ct_decrypt_lift: the destination range overlaps an input");
+    u64* maxd = nullptr;
+    int rc;
+    if ((rc = maxd_get(r, max_digits, batch, &maxd)) != ALCH_OK) return rc;
+    alch_ring* rd = dst_zp ? dst_zp->ring : nullptr;
+    if (rd && (rc = ext_order(r, rd, true)) != ALCH_OK) return rc;
+    rc = ALCH_BY_WORD(r, do_decrypt, r, in->dptr, batch, degree, sk, s_pre, nullptr, rd, d, l_scalar, maxd, (flags & ALCH_POW_IN) != 0);
+    if (rc != ALCH_OK) return rc;
+    if (rd && (rc = ext_order(r, rd, false)) != ALCH_OK) return rc;
+    return maxd_fetch(r, max_digits, batch);
 } catch (...) { return abi_catch(); }
 
 #include "tensor_ext.inc.hpp"

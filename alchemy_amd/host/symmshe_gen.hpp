@@ -3,7 +3,7 @@
 // (Crypto/Alchemy/Interpreter/Eval.hs:120-134), plus the key / hint generation of Crypto/Alchemy/Interpreter/KeysHints.hs:
 //
 //   SK, genSK                                (KeysHints.hs:86-96:  svar = r / sqrt(phi(m')))
-//   encrypt, decrypt, errorTermUnrestricted   (PT2CT.hs:84-99, Eval.hs:151-160)
+//   encrypt, decrypt, errorTermUnrestricted   (PT2CT.hs:84-99, Eval.hs:151-160); decryptBatch / errorRatesBatch on resident batches
 //   toLSD / toMSD, (*), addPublic, mulPublic, modSwitchPT, modSwitch, keySwitchQuadCirc, tunnel   (Eval.hs:65-67,129-134)
 //   ksQuadCircHint, tunnelHint               (KeysHints.hs:101-129)
 //
@@ -360,6 +360,82 @@ struct DevBatch {
         enc = Encoding::MSD;
     }
 };
+
+// ---- decrypt and errorRate_ on a resident batch (alch_ct_decrypt_lift; the per-element `decrypt` above is the reference form) ----
+// |x| / Q of one mixed-radix digit vector x = d_0 + q_0 (d_1 + q_1 (d_2 + ...)) as the library returns it (limb 0 least significant):
+// x / Q = ((d_0 / q_0 + d_1) / q_1 + d_2) / q_2 ..., every partial value below 1.
+inline long double digitsOverQ(const uint64_t* d, const std::vector<uint64_t>& qs) {
+    long double v = 0;
+    for (size_t j = 0; j < qs.size(); ++j) v = ((long double)d[j] + v) / (long double)qs[j];
+    return v;
+}
+
+// The secret key as one CRT-basis element in HBM (what alch_ct_error_term / alch_ct_decrypt_lift take); the caller frees it.
+inline alch_buf* keyToDevice(const Ring& r, const SK& sk) {
+    const Cyc s = Cyc::fromIntegers(r, sk.s).toCRT();
+    alch_buf* b = nullptr;
+    check(alch_buf_alloc(r.handle(), 1, &b), "alch_buf_alloc");
+    if (s.onDeviceOnly()) check(alch_buf_copy(b, 0, s.dev(), 0, 1), "alch_buf_copy");
+    else check(alch_buf_upload(b, 0, 1, s.data().data()), "alch_buf_upload");
+    return b;
+}
+
+// The per-limb scalar and the Z_p scalar of the batch's LSD form, without touching the batch (toLSD rides on the call).
+inline std::vector<uint64_t> lsdFormOf(const DevBatch& x, int64_t& l_lsd) {
+    l_lsd = x.l;
+    if (x.enc == Encoding::LSD) return std::vector<uint64_t>(x.ring->qs().size(), 1);
+    l_lsd = (int64_t)(((i128)x.l * invmod_any(neg_q_mod_p(x.ring->qs(), x.p), x.p)) % x.p);
+    return lsdScalars(x.ring->qs(), x.p);
+}
+
+// errorRate_ of every ciphertext of the batch: max |liftDec c(s)| / q, from the device's exact digit vectors.
+inline std::vector<double> errorRatesBatch(const SK& sk, const DevBatch& x) {
+    int64_t l_lsd = 1;
+    const std::vector<uint64_t> s = lsdFormOf(x, l_lsd);
+    const size_t L = x.ring->qs().size();
+    std::vector<uint64_t> digits(x.B * L);
+    alch_buf* key = keyToDevice(*x.ring, sk);
+    const int rcl = alch_ct_decrypt_lift(x.buf, x.B, 1, key, 0, s.data(), nullptr, 0, 1, digits.data(), x.basis == Basis::Pow ? ALCH_POW_IN : 0u);
+    alch_buf_free(key);
+    check(rcl, "alch_ct_decrypt_lift");
+    std::vector<double> rates(x.B);
+    for (size_t b = 0; b < x.B; ++b) rates[b] = (double)digitsOverQ(&digits[b * L], x.ring->qs());
+    return rates;
+}
+
+// decrypt of every ciphertext of the batch: l * twace(g^-k (liftDec(c(s)) mod p)) on the Pow basis; false when a divG fails.
+// One alch_ct_decrypt_lift call, then divG / twace / l on the Z_p rings; only the plaintexts (and the digit vectors) cross to the host.
+inline bool decryptBatch(RingCache& rc, const SK& sk, const DevBatch& x, std::vector<PtCyc>& out, std::vector<double>* error_rates = nullptr) {
+    int64_t l_lsd = 1;
+    const std::vector<uint64_t> s = lsdFormOf(x, l_lsd);
+    const Ring& r = *x.ring;
+    const size_t L = r.qs().size();
+    const Ring& zp = rc.get(r.m(), {(uint64_t)x.p}, false);
+    const Ring& zs = rc.get(x.m, {(uint64_t)x.p}, false);
+    std::vector<uint64_t> digits(error_rates ? x.B * L : 0);
+    alch_buf *key = keyToDevice(r, sk), *big = nullptr, *small = nullptr;
+    check(alch_buf_alloc(zp.handle(), x.B, &big), "alch_buf_alloc");
+    check(alch_buf_alloc(zs.handle(), x.B, &small), "alch_buf_alloc");
+    auto release = [&]() { alch_buf_free(key); alch_buf_free(big); alch_buf_free(small); };
+    int rcl = alch_ct_decrypt_lift(x.buf, x.B, 1, key, 0, s.data(), big, 0, (uint64_t)l_lsd, error_rates ? digits.data() : nullptr,
+                                   x.basis == Basis::Pow ? ALCH_POW_IN : 0u);
+    for (int i = 0; i < x.k && rcl == ALCH_OK; ++i) rcl = alch_buf_divg(big, 0, x.B, ALCH_BASIS_DEC);
+    if (rcl == ALCH_OK) rcl = alch_buf_twace(small, big, x.B, ALCH_BASIS_DEC);
+    if (rcl == ALCH_OK) rcl = alch_buf_l(small, 0, x.B);
+    out.clear();
+    for (size_t b = 0; b < x.B && rcl == ALCH_OK; ++b) {
+        out.push_back(PtCyc{x.m, x.p, Basis::Pow, std::vector<int64_t>(zs.n())});
+        rcl = alch_buf_download(small, b, 1, out.back().v.data());
+    }
+    release();
+    if (rcl == ALCH_NOT_DIVISIBLE) return false;
+    check(rcl, "decryptBatch");
+    if (error_rates) {
+        error_rates->resize(x.B);
+        for (size_t b = 0; b < x.B; ++b) (*error_rates)[b] = (double)digitsOverQ(&digits[b * L], r.qs());
+    }
+    return true;
+}
 
 // addPublic b on every ciphertext of the batch (LSD form)
 inline void addPublicBatch(PtOps& ops, DevBatch& x, const PtCyc& b) {

@@ -13,7 +13,10 @@
 // max |c(s)| / q -- what the ERW interpreter logs (Crypto/Alchemy/Interpreter/ErrorRateWriter.hs:70-75, Eval.hs:151-160) -- is printed.
 //
 //   homomrlwr_replay [batch] [--seed N] [--dump DIR] [--per-element] [--per-element-resident] [--per-element-zip-host]
-//                    [--host-mode buffers|resident] [--var-scale F] [--quiet-stages]
+//                    [--host-mode buffers|resident] [--var-scale F] [--quiet-stages] [--device-decrypt]
+// --device-decrypt runs the closing check (decrypt and error rate of every result) through decryptBatch -- one alch_ct_decrypt_lift
+// call on the resident batch, then divG / twace / l on the plaintext rings -- instead of one host-side decrypt per ciphertext; the
+// PASS line and the statistics are the same.
 // --dump writes the final ciphertexts, the H5' key and the expected plaintexts for an independent decryption by the oracle
 // (tests/test_gpu_homomrlwr_full.py).  The --per-element* flags also run the first hop (modSwitch . tunnel hint . modSwitch) through
 // the per-Tensor-call path -- what `eval` over `instance Tensor GT` issues, one C-ABI call per Tensor method -- in the three
@@ -55,7 +58,7 @@ int main(int argc, char** argv) {
     size_t B = 4;
     uint64_t seed = 2026;
     std::string dump;
-    bool per_element = false, per_resident = false, per_ziphost = false, quiet = false;
+    bool per_element = false, per_resident = false, per_ziphost = false, quiet = false, device_decrypt = false;
     double var_scale = 1.0;
     Mode host_mode = Mode::Resident;
     for (int i = 1; i < argc; ++i) {
@@ -65,6 +68,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--per-element-resident")) per_resident = true;
         else if (!strcmp(argv[i], "--per-element-zip-host")) per_ziphost = true;
         else if (!strcmp(argv[i], "--quiet-stages")) quiet = true;
+        else if (!strcmp(argv[i], "--device-decrypt")) device_decrypt = true;
         else if (!strcmp(argv[i], "--var-scale") && i + 1 < argc) var_scale = atof(argv[++i]);
         else if (!strcmp(argv[i], "--host-mode") && i + 1 < argc) host_mode = !strcmp(argv[++i], "buffers") ? Mode::HostBuffers : Mode::Resident;
         else B = (size_t)atoi(argv[i]);
@@ -256,10 +260,15 @@ int main(int argc, char** argv) {
         size_t good = 0;
         double worst = 0, mean = 0;
         std::vector<double> rates;
+        std::vector<PtCyc> dev_got;
+        std::vector<double> dev_er;
+        const bool dev_ok = device_decrypt && decryptBatch(rc, sk[5], res, dev_got, &dev_er);
         for (size_t b = 0; b < B; ++b) {
             PtCyc got;
             double er = 0;
-            if (decrypt(rc, ops, sk[5], res.download(b), got, &er) && got.p == expect[b].p && got.v == ops.to(expect[b], Basis::Pow).v) ++good;
+            if (device_decrypt) {
+                if (dev_ok) { er = dev_er[b]; if (dev_got[b].p == expect[b].p && dev_got[b].v == ops.to(expect[b], Basis::Pow).v) ++good; }
+            } else if (decrypt(rc, ops, sk[5], res.download(b), got, &er) && got.p == expect[b].p && got.v == ops.to(expect[b], Basis::Pow).v) ++good;
             worst = std::max(worst, er);
             mean += er / (double)B;
             rates.push_back(er);

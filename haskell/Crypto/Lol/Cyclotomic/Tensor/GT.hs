@@ -57,12 +57,13 @@
 -- that of lol-cpp's pointwise loop (INTEGRATION.md section 3: 91 per second against 1 084 with everything resident).  'mulGT',
 -- 'addGT', 'subGT' are the device forms (also the @Additive@ instance of @GT m r@): a Lol whose @UCyc@ instances call them
 -- instead of @zipWithT (*)@ / @(+)@ / @(-)@ -- a three-line change in Lol, none in ALCHEMY -- keeps whole ciphertext operations
--- in HBM.  The batched entry points at the end ('mulRelinGT', 'mulFullGT', 'tunnelGT', 'modSwitchGT') are the fast path proper.
+-- in HBM.  The batched entry points at the end ('mulRelinGT', 'mulFullGT', 'tunnelGT', 'modSwitchGT', 'decryptLiftGT') are the fast path proper.
 --
 -- Use: @import Crypto.Lol.Cyclotomic.Tensor.GT@ instead of @...Tensor.CPP@ and write @GT@ for @CT@ in the plaintext alias
 -- (reference examples/Arithmetic.hs:19,23; @haskell/examples/Arithmetic-GT.patch@).  Nothing in @Crypto.Alchemy.*@ changes.
 module Crypto.Lol.Cyclotomic.Tensor.GT
-  ( GT, GTDispatch(..), toDeviceGT, toHostGT, mulGT, addGT, subGT, mulRelinGT, mulFullGT, tunnelGT, modSwitchGT ) where
+  ( GT, GTDispatch(..), toDeviceGT, toHostGT, mulGT, addGT, subGT, mulRelinGT, mulFullGT, tunnelGT, modSwitchGT,
+    errorTermGT, liftGT, decryptLiftGT ) where
 
 import Control.DeepSeq                         (NFData (..))
 import Control.Monad                           (when)
@@ -506,6 +507,24 @@ mulRelinGT ring hint a b out batch spre =
 mulFullGT :: Ptr AlchHint -> Ptr AlchBuf -> Ptr AlchBuf -> Ptr AlchBuf -> Int -> [Word64] -> IO ()
 mulFullGT hint a b out batch spre =
   withArray spre $ \ps -> c_ctMulFull hint a b out (fromIntegral batch) ps 0 >>= check "alch_ct_mul_full"
+
+-- | @c(s)@ of a device-resident batch on the decoding basis -- the object @errorTermUnrestricted@ lifts (reference Eval.hs:150-160):
+-- one 'c_ctErrorTerm' call.  Arguments: ciphertext buffer ((degree+1)*batch CRT-basis elements), batch, degree (1 or 2), the key as
+-- a one-element CRT-basis buffer, toLSD's per-limb scalar, output buffer (batch elements).
+errorTermGT :: Ptr AlchBuf -> Int -> Int -> Ptr AlchBuf -> [Word64] -> Ptr AlchBuf -> IO ()
+errorTermGT cts batch deg sk spre out =
+  withArray spre $ \ps -> c_ctErrorTerm cts (fromIntegral batch) (fromIntegral deg) sk 0 ps out 0 0 >>= check "alch_ct_error_term"
+
+-- | Centred lift of @count@ Pow- or Dec-basis elements: residues @l * (lift mod p)@ into a buffer of the Z_p ring over the same
+-- index, and the mixed-radix digits of @max |lift|@ of every element (@count * L@ words, limb 0 least significant).
+liftGT :: Ptr AlchBuf -> Int -> Ptr AlchBuf -> Word64 -> Ptr Word64 -> IO ()
+liftGT src count dst l digits = c_bufLift src 0 (fromIntegral count) dst 0 l digits >>= check "alch_buf_lift"
+
+-- | What @decrypt@ (reference PT2CT.hs:91-99) and @errorRate_@ need of a device-resident batch, in one 'c_ctDecryptLift' call:
+-- @l * (liftDec (c(s)) mod p)@ into the Z_p buffer and the digit vectors of @max |liftDec (c(s))|@.
+decryptLiftGT :: Ptr AlchBuf -> Int -> Int -> Ptr AlchBuf -> [Word64] -> Ptr AlchBuf -> Word64 -> Ptr Word64 -> IO ()
+decryptLiftGT cts batch deg sk spre dst l digits =
+  withArray spre $ \ps -> c_ctDecryptLift cts (fromIntegral batch) (fromIntegral deg) sk 0 ps dst 0 l digits 0 >>= check "alch_ct_decrypt_lift"
 
 -- | @tunnel hint@ on device-resident batches of linear ciphertexts (SymmSHE tunnel as E runs it, reference Eval.hs:134): one
 -- 'c_ctTunnel' call.  PT2CT emits @modSwitch_ .: tunnel_ hint .: modSwitch_@ (PT2CT.hs:224-229): when the input buffer's ring holds

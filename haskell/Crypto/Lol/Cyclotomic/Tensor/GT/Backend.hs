@@ -126,6 +126,11 @@ foreign import ccall safe   "alch_ct_tunnel"           c_ctTunnel        :: Ptr 
 
 foreign import ccall safe   "alch_ct_mod_switch"       c_ctModSwitch     :: Ptr AlchBuf -> Ptr AlchBuf -> CSize -> CUInt -> IO CInt
 
+-- decrypt / errorRate_ on resident batches (library version 1.8): c(s) on the decoding basis, the centred lift, and both in one call
+foreign import ccall safe   "alch_ct_error_term"       c_ctErrorTerm     :: Ptr AlchBuf -> CSize -> CInt -> Ptr AlchBuf -> CSize -> Ptr Word64 -> Ptr AlchBuf -> CSize -> CUInt -> IO CInt
+foreign import ccall safe   "alch_buf_lift"            c_bufLift         :: Ptr AlchBuf -> CSize -> CSize -> Ptr AlchBuf -> CSize -> Word64 -> Ptr Word64 -> IO CInt
+foreign import ccall safe   "alch_ct_decrypt_lift"     c_ctDecryptLift   :: Ptr AlchBuf -> CSize -> CInt -> Ptr AlchBuf -> CSize -> Ptr Word64 -> Ptr AlchBuf -> CSize -> Word64 -> Ptr Word64 -> CUInt -> IO CInt
+
 -- the hot path: keySwitchQuadCirc hint (a * b), and PT2CT's whole mul_
 foreign import ccall safe   "alch_ct_mul_relin"        c_ctMulRelin      :: Ptr AlchRing -> Ptr AlchHint -> Ptr AlchBuf -> Ptr AlchBuf -> Ptr AlchBuf -> CSize -> Ptr Word64 -> CUInt -> IO CInt
 foreign import ccall safe   "alch_ct_mul_full"         c_ctMulFull       :: Ptr AlchHint -> Ptr AlchBuf -> Ptr AlchBuf -> Ptr AlchBuf -> CSize -> Ptr Word64 -> CUInt -> IO CInt

@@ -81,7 +81,7 @@ typedef struct alch_tunnel alch_tunnel;
 #define ALCH_GAD_BASE2 1           /* BaseBGad 2: sum_i ceil(log2 q_i) digits; unfused device path */
 
 const char *alch_last_error(void);
-/* Library/ABI version: (major<<16)|minor; the minor number goes up with every added capability (1.7: tunnels between two-power rings). */
+/* Library/ABI version: (major<<16)|minor; the minor number goes up with every added capability (1.7: tunnels between two-power rings; 1.8: decrypt / error rates on resident batches). */
 uint32_t alch_version(void);
 
 /* ---- ring context ------------------------------------------------------------------------------
@@ -416,6 +416,35 @@ int alch_ct_tunnel(const alch_tunnel *t, const alch_buf *in, alch_buf *out, size
  *   out has fewer limbs: Rescale (a, b) -> b per dropped limb (any number), c0 rescaled on the Dec basis and c1 on the Pow basis
  *   (Lol: rescaleDec / rescalePow); CRT basis in and out unless ALCH_POW_IN / ALCH_POW_OUT.  The input is not modified. */
 int alch_ct_mod_switch(const alch_buf *in, alch_buf *out, size_t batch, unsigned flags);
+
+/* ---- decrypt and errorRate_ on resident ciphertext batches (since 1.8) -------------------------------------------------
+ * SymmSHE decrypt (Crypto/Alchemy/Interpreter/PT2CT.hs:91-99) and errorTermUnrestricted as the ErrorRateWriter interpreter logs it
+ * (Eval.hs:150-160) both start from c(s), the ciphertext polynomial evaluated at the secret key, on the decoding basis, and lift
+ * it, centred, from Z_q to the integers.  The lift never leaves word arithmetic: the mixed-radix (Garner) digits
+ * x = d_0 + q_0 (d_1 + q_1 (d_2 + ...)), d_j in [0, q_j), are compared with ((q_j - 1)/2)_j from the top limb down (all moduli are
+ * odd, so there is no tie), and |x| is again a digit vector.  What is left of decrypt stays composed from alch_buf_divg (k times,
+ * on the Z_p ring), alch_buf_twace and alch_buf_l; `l_scalar` commutes with all of them and is folded into the lift.
+ * Work is queued on the source ring's stream; a destination ring on another stream is ordered before and after it, as
+ * alch_ct_mul_full orders its three rings.  batch = 0 / count = 0: ALCH_OK, nothing done.  max_digits is a HOST array, filled when
+ * the call returns (one synchronisation of the stream; none without it). */
+/* out[out_first + b] = c_b(s) for b < batch: ciphertext b = elements ((degree+1) b ..) of `in`; degree 1 or 2; sk = element
+ * sk_index of sk_crt (CRT basis, same ring); s_pre = toLSD's per-limb scalar (NULL = 1).  CRT basis in (ALCH_POW_IN: Pow);
+ * result on the DECODING basis (crtInv, then lInv on a general index) -- the object errorTermUnrestricted lifts.  Input untouched. */
+int alch_ct_error_term(const alch_buf *in, size_t batch, int degree, const alch_buf *sk_crt, size_t sk_index,
+                       const uint64_t *s_pre, alch_buf *out, size_t out_first, unsigned flags);
+
+/* Centred lift mod Q = prod q_j of every coefficient of src[first .. first+count) (Pow or Dec basis; the basis is the caller's).
+ *   dst_zp (nullable): a ring of the SAME index with ONE modulus p (alch_ring_create_nocrt or a CRT ring): element dst_first + i
+ *                      = l_scalar * (lift mod p) mod p.
+ *   max_digits (nullable): count * L words; the mixed-radix digits (limb 0 least significant) of max_k |lift| of each element. */
+int alch_buf_lift(const alch_buf *src, size_t first, size_t count, alch_buf *dst_zp, size_t dst_first, uint64_t l_scalar,
+                  uint64_t *max_digits);
+
+/* Both in one call for a batch of ciphertexts -- what decrypt and errorRate_ need.  c(s) stays in a scratch area the ring keeps
+ * (at most 1 GiB; larger batches are walked in chunks of that size), so nothing but the residues and the digits is written. */
+int alch_ct_decrypt_lift(const alch_buf *in, size_t batch, int degree, const alch_buf *sk_crt, size_t sk_index,
+                         const uint64_t *s_pre, alch_buf *dst_zp, size_t dst_first, uint64_t l_scalar, uint64_t *max_digits,
+                         unsigned flags);
 
 /* ---- modSwitch building block (Eval.hs:130) ---------------------------------------
  * Rescale (a,b) -> b on Pow-basis elements: src lives in ring_src (L limbs), dst in ring_dst whose
