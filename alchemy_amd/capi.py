@@ -37,6 +37,7 @@ SYMBOLS = [
     "alch_twace_pow_dec", "alch_twace_crt", "alch_coeffs", "alch_ext_table", "alch_crt_set_dec", "alch_ct_add_public",
     "alch_ring_share_stream", "alch_buf_copy", "alch_buf_tensor_op", "alch_buf_view", "alch_buf_ring", "alch_ring_device",
     "alch_ct_error_term", "alch_buf_lift", "alch_ct_decrypt_lift",
+    "alch_ct_mul", "alch_ct_key_switch_quad", "alch_ct_mod_switch_deg",
 ]
 
 
@@ -160,6 +161,9 @@ def load_library():
         "alch_ct_error_term": [VP, C.c_size_t, C.c_int, VP, C.c_size_t, PU64, VP, C.c_size_t, C.c_uint],
         "alch_buf_lift": [VP, C.c_size_t, C.c_size_t, VP, C.c_size_t, C.c_uint64, PU64],
         "alch_ct_decrypt_lift": [VP, C.c_size_t, C.c_int, VP, C.c_size_t, PU64, VP, C.c_size_t, C.c_uint64, PU64, C.c_uint],
+        "alch_ct_mul": [VP, VP, VP, VP, C.c_size_t, PU64, C.c_uint],
+        "alch_ct_key_switch_quad": [VP, VP, VP, C.c_size_t, PU64, C.c_uint],
+        "alch_ct_mod_switch_deg": [VP, VP, C.c_size_t, C.c_int, C.c_uint],
     }
     for name, args in sig.items():
         fn = getattr(l, name)

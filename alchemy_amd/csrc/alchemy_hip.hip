@@ -171,6 +171,10 @@ static thread_local std::string g_err;
 // element ranges of the C ABI are checked without forming first + count or 2 * batch (a huge argument must not wrap past the check)
 static inline bool range_ok(size_t first, size_t count, size_t n) { return count <= n && first <= n - count; }
 static inline bool pairs_ok(size_t batch, size_t n) { return batch <= n / 2; }
+static bool bytes_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const char *x = reinterpret_cast<const char*>(a), *y = reinterpret_cast<const char*>(b);
+    return x < y + nb && y < x + na;
+}
 static int fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
@@ -462,6 +466,63 @@ __global__ void k_tensor_ew(DevRing<W> R, const W* a, const W* b, W* out, W* c2b
         if (!c2_compact) *reinterpret_cast<P*>(c2buf + ct * Ln + rem) = c2;
         else if (rem >= off) *reinterpret_cast<P*>(c2buf + ct * Lsn + (rem - off)) = c2;
         if (c2crt) *reinterpret_cast<P*>(c2crt + ct * Ln + rem) = c2;
+    }
+}
+
+// SymmSHE (*) as a step of its own (alch_ct_mul): the quadratic ciphertext of slot ct goes straight to elements (3 ct, 3 ct + 1, 3 ct + 2)
+// of out = (c0, c1, c2) -- the layout alch_ct_error_term reads for degree 2.  a, b and out live on one ring; sr2 = s R^2, gt as above.
+template <typename W, int VW = 1>
+__global__ void k_ct_tensor3(DevRing<W> R, const W* a, const W* b, W* out, size_t nct, Scal<W> sr2, GTab<W> gt) {
+    typedef Pack<W, VW> P;
+    const size_t n = (size_t)R.n, Ln = (size_t)R.L * n;
+    ALCH_WALK_INIT(R.n / VW, R.L);
+    ALCH_WALK(w, nct * Ln / VW, wk) {
+        const size_t ct = wk.outer, rem = (size_t)wk.mid * n + (size_t)wk.k * VW;
+        const ModP<W> m = R.mod[wk.mid];
+        const W s = sr2.v[wk.mid];
+        const P a0 = *reinterpret_cast<const P*>(a + 2 * ct * Ln + rem), a1 = *reinterpret_cast<const P*>(a + (2 * ct + 1) * Ln + rem);
+        const P b0 = *reinterpret_cast<const P*>(b + 2 * ct * Ln + rem), b1 = *reinterpret_cast<const P*>(b + (2 * ct + 1) * Ln + rem);
+        const W* g = gt.p[wk.mid];
+        P gv, c0, c1, c2;
+        if (g) gv = *reinterpret_cast<const P*>(g + (size_t)wk.k * VW);
+#pragma unroll
+        for (int c = 0; c < VW; ++c) {
+            const W x0 = mont_mul(a0.v[c], s, m), x1 = mont_mul(a1.v[c], s, m);                          // a s R
+            W c0v = mont_mul(b0.v[c], x0, m);
+            W c1v = add_mod(mont_mul(b1.v[c], x0, m), mont_mul(b0.v[c], x1, m), m.q);
+            W c2v = mont_mul(b1.v[c], x1, m);
+            if (g) { c0v = mont_mul(c0v, gv.v[c], m); c1v = mont_mul(c1v, gv.v[c], m); c2v = mont_mul(c2v, gv.v[c], m); }
+            c0.v[c] = c0v; c1.v[c] = c1v; c2.v[c] = c2v;
+        }
+        W* o = out + 3 * ct * Ln + rem;
+        *reinterpret_cast<P*>(o) = c0;
+        *reinterpret_cast<P*>(o + Ln) = c1;
+        *reinterpret_cast<P*>(o + 2 * Ln) = c2;
+    }
+}
+
+// The way into keySwitchQuadCirc as a step of its own (alch_ct_key_switch_quad): the components of `nct` quadratic ciphertexts
+// (elements 3 ct ..) times toMSD's scalar (sm = s R; scale = 0: s = 1, plain copies): (c0, c1) -> pair [ct][2], c2 -> c2a [ct] and,
+// when given, a second copy c2b (the one that stays in the CRT basis).
+template <typename W, int VW = 1>
+__global__ void k_ct_split3(DevRing<W> R, const W* in, W* pair, W* c2a, W* c2b, size_t nct, Scal<W> sm, int scale) {
+    typedef Pack<W, VW> P;
+    const size_t n = (size_t)R.n, Ln = (size_t)R.L * n;
+    ALCH_WALK_INIT(R.n / VW, R.L);
+    ALCH_WALK(w, nct * Ln / VW, wk) {
+        const size_t ct = wk.outer, rem = (size_t)wk.mid * n + (size_t)wk.k * VW;
+        const W* i = in + 3 * ct * Ln + rem;
+        P c0 = *reinterpret_cast<const P*>(i), c1 = *reinterpret_cast<const P*>(i + Ln), c2 = *reinterpret_cast<const P*>(i + 2 * Ln);
+        if (scale) {
+            const ModP<W> m = R.mod[wk.mid];
+            const W s = sm.v[wk.mid];
+#pragma unroll
+            for (int c = 0; c < VW; ++c) { c0.v[c] = mont_mul(c0.v[c], s, m); c1.v[c] = mont_mul(c1.v[c], s, m); c2.v[c] = mont_mul(c2.v[c], s, m); }
+        }
+        *reinterpret_cast<P*>(pair + 2 * ct * Ln + rem) = c0;
+        *reinterpret_cast<P*>(pair + (2 * ct + 1) * Ln + rem) = c1;
+        *reinterpret_cast<P*>(c2a + ct * Ln + rem) = c2;
+        if (c2b) *reinterpret_cast<P*>(c2b + ct * Ln + rem) = c2;
     }
 }
 
@@ -2517,6 +2578,8 @@ struct KsStage {
     const alch_hint* hint;
     int dup;                    // leading limbs of r the operands lack: the modSwitch up of alch_ct_mul_full, folded in
     bool have_c2;               // c2 arrives on the powerful basis of r: no tensor product, no c2 scratch
+    bool c2_both;               // with have_c2: the caller filled the stage's own layout -- c2 (Pow) at scratch, its CRT copy behind it, digits after
+                                // both (alch_ct_key_switch_quad: the TrivGad forms below read the diagonal digits from the CRT copy)
     bool base2;
     bool fused_digits;          // TrivGad: decompose + reduce in the digit transforms' loader; the diagonal digits are c2's CRT copy
     bool gen_fused;             // k_gen_tensor_inv + k_gen_ks
@@ -2555,8 +2618,8 @@ static int ks_stage(alch_ring* r, const KsStage<W>& s, const W* a, const W* b, c
     const int L = r->L, Ls = L - s.dup;
     const W* hint = reinterpret_cast<const W*>(s.hint->dptr);
     char* c2crt = s.scratch + s.chunk * eb;                       // CRT-basis copy of c2 (diagonal digits, split rings)
-    W* dig = reinterpret_cast<W*>(s.have_c2 ? s.scratch : c2crt + s.chunk * eb);
-    W* diag = s.fused_digits ? reinterpret_cast<W*>(c2crt) : nullptr;
+    W* dig = reinterpret_cast<W*>(s.have_c2 && !s.c2_both ? s.scratch : c2crt + s.chunk * eb);
+    W* diag = s.fused_digits ? reinterpret_cast<W*>(c2crt) : nullptr;   // have_c2 without c2_both: BaseBGad 2 only (no diagonal)
     NttCall<W> nc{};
     nc.ring = &dev_ring<W>(r); nc.stream = r->stream; nc.balanced = r->balanced;
     GenCall<W> gc{};
@@ -2790,6 +2853,122 @@ extern "C" int alch_ct_mul_relin(alch_ring* r, const alch_hint* hint, const alch
     return ALCH_OK;
 } catch (...) { return abi_catch(); }
 
+// ---- mul_ one SHE operation at a time (within ABI 1.8; a host probes for the symbols): (*) and keySwitchQuadCirc on their own -----
+// PT2CT emits modSwitch_ . keySwitchQuad_ hint . modSwitch_ $ x *: y as four object-language operations (PT2CT.hs:160-177) and the
+// ErrorRateWriter logs a rate after each; these entry points let the quadratic ciphertext exist in a caller's buffer, elements
+// (3b, 3b+1, 3b+2) = (c0, c1, c2).  They are the inspection path: alch_ct_mul_relin / alch_ct_mul_full stay the fast one.
+template <typename W>
+static int do_ct_mul(alch_ring* r, const void* a, const void* b, void* out, size_t batch, const uint64_t* s_pre, unsigned flags) {
+    Scal<W> sr2;
+    scal_to_mont<W>(r, s_pre, 2, sr2);
+    const GTab<W> gt = g_table<W>(r);
+    const size_t eb = elem_bytes(r), ew = elem_words(r);
+    const bool pow_in = (flags & ALCH_POW_IN) != 0;
+    size_t chunk = batch;
+    int rc;
+    if (pow_in) {                                          // CRT copies of one chunk's operands: 2 + 2 elements per ciphertext
+        chunk = std::min(batch, std::max<size_t>(1, (r->scratch_mib << 20) / (4 * eb)));
+        if ((rc = ensure_ws(&r->ws_in, &r->ws_in_bytes, chunk * 4 * eb)) != ALCH_OK) return rc;
+    }
+    for (size_t done = 0; done < batch; done += chunk) {
+        const size_t now = std::min(chunk, batch - done);
+        const W* pa = reinterpret_cast<const W*>(a) + done * 2 * ew;
+        const W* pb = reinterpret_cast<const W*>(b) + done * 2 * ew;
+        if (pow_in) {
+            char* wa = reinterpret_cast<char*>(r->ws_in);
+            char* wb = wa + now * 2 * eb;
+            if (split_ring(r)) {                           // the split transform works in place: copy first
+                HIP_TRY(hipMemcpyAsync(wa, pa, now * 2 * eb, hipMemcpyDeviceToDevice, r->stream));
+                HIP_TRY(hipMemcpyAsync(wb, pb, now * 2 * eb, hipMemcpyDeviceToDevice, r->stream));
+                rc = do_crt<W>(r, wa, 0, 4 * now, false);
+            } else if ((rc = do_crt<W>(r, wa, 0, 2 * now, false, pa)) == ALCH_OK)
+                rc = do_crt<W>(r, wb, 0, 2 * now, false, pb);
+            if (rc != ALCH_OK) return rc;
+            pa = reinterpret_cast<const W*>(wa);
+            pb = reinterpret_cast<const W*>(wb);
+        }
+        ALCH_LAUNCH_VW(k_ct_tensor3, r, now * ew, r->stream, dev_ring<W>(r), pa, pb, reinterpret_cast<W*>(out) + done * 3 * ew, now, sr2, gt);
+        HIP_TRY(hipGetLastError());
+        if ((flags & ALCH_POW_OUT) && (rc = do_crt<W>(r, out, 3 * done, 3 * now, true)) != ALCH_OK) return rc;
+    }
+    return ALCH_OK;
+}
+
+extern "C" int alch_ct_mul(alch_ring* r, const alch_buf* a, const alch_buf* b, alch_buf* out, size_t batch, const uint64_t* s_pre,
+                           unsigned flags) try {
+    if (!r || !a || !b || !out) return fail(ALCH_E_INVALID, "alch_ct_mul: null argument");
+    if (a->ring != r || b->ring != r || out->ring != r) return fail(ALCH_E_INVALID, "alch_ct_mul: handles belong to different rings");
+    if (!pairs_ok(batch, a->n_elems) || !pairs_ok(batch, b->n_elems) || batch > out->n_elems / 3)
+        return fail(ALCH_E_INVALID, "alch_ct_mul: operands must hold 2*batch ring elements, out 3*batch");
+    if (flags & ~(unsigned)(ALCH_POW_IN | ALCH_POW_OUT)) return fail(ALCH_E_INVALID, "alch_ct_mul: unknown flag");
+    if (out == a || out == b || bytes_overlap(out->dptr, 3 * batch * elem_bytes(r), a->dptr, 2 * batch * elem_bytes(r)) ||
+        bytes_overlap(out->dptr, 3 * batch * elem_bytes(r), b->dptr, 2 * batch * elem_bytes(r)))
+        return fail(ALCH_E_INVALID, "alch_ct_mul: out must not alias an input");
+    if (!r->has_crt) return fail(ALCH_E_NO_CRT, "alch_ct_mul: this ring has no CRT basis");
+    if (batch == 0) return ALCH_OK;
+    BIND(r);
+    return ALCH_BY_WORD(r, do_ct_mul, r, a->dptr, b->dptr, out->dptr, batch, s_pre, flags);
+} catch (...) { return abi_catch(); }
+
+// keySwitchQuadCirc from a resident quadratic ciphertext, through the composed stage (ks_stage with a ready c2).  Per chunk:
+// k_ct_split3 scales and gathers (c0, c1) into out and c2 into the stage's scratch (twice for the forms that read the diagonal digits
+// from a CRT copy: the input is in the CRT basis, so that copy costs a store), crtInv of c2 in place, then the stage's ladder.
+template <typename W>
+static int do_key_switch_quad(alch_ring* r, const alch_hint* hint, const void* in, void* out, size_t batch, const uint64_t* s_pre,
+                              unsigned flags) {
+    KsStage<W> s = ks_stage_plan<W>(r, hint, 0, true);
+    s.c2_both = true;
+    const size_t eb = elem_bytes(r), ew = elem_words(r);
+    const bool pow_in = (flags & ALCH_POW_IN) != 0;
+    // scratch per ciphertext: c2 in both bases + the stage's digits (+ the CRT copy of a Pow-basis input)
+    const size_t stage_elems = 2 + s.elems;
+    const size_t per_ct = (stage_elems + (pow_in ? 3 : 0)) * eb;
+    s.chunk = std::min(batch, std::max<size_t>(1, (r->scratch_mib << 20) / per_ct));
+    int rc = ensure_ws(&r->ws_digits, &r->ws_digits_bytes, s.chunk * per_ct);
+    if (rc != ALCH_OK) return rc;
+    s.scratch = reinterpret_cast<char*>(r->ws_digits);
+    W* c2pow = reinterpret_cast<W*>(s.scratch);
+    W* c2crt = s.fused_digits ? reinterpret_cast<W*>(s.scratch + s.chunk * eb) : nullptr;
+    char* win = s.scratch + s.chunk * stage_elems * eb;
+    Scal<W> sm;
+    scal_to_mont<W>(r, s_pre, 1, sm);
+    for (size_t done = 0; done < batch; done += s.chunk) {
+        const size_t now = std::min(s.chunk, batch - done);
+        const W* src = reinterpret_cast<const W*>(in) + done * 3 * ew;
+        if (pow_in) {
+            if (split_ring(r)) {                           // the split transform works in place: copy first
+                HIP_TRY(hipMemcpyAsync(win, src, now * 3 * eb, hipMemcpyDeviceToDevice, r->stream));
+                rc = do_crt<W>(r, win, 0, 3 * now, false);
+            } else rc = do_crt<W>(r, win, 0, 3 * now, false, src);
+            if (rc != ALCH_OK) return rc;
+            src = reinterpret_cast<const W*>(win);
+        }
+        W* po = reinterpret_cast<W*>(out) + done * 2 * ew;
+        ALCH_LAUNCH_VW(k_ct_split3, r, now * ew, r->stream, dev_ring<W>(r), src, po, c2pow, c2crt, now, sm, s_pre ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+        if ((rc = do_crt<W>(r, c2pow, 0, now, true)) != ALCH_OK) return rc;
+        if ((rc = ks_stage<W>(r, s, nullptr, nullptr, c2pow, po, now)) != ALCH_OK) return rc;
+        if ((flags & ALCH_POW_OUT) && (rc = do_crt<W>(r, out, 2 * done, 2 * now, true)) != ALCH_OK) return rc;
+    }
+    return ALCH_OK;
+}
+
+extern "C" int alch_ct_key_switch_quad(const alch_hint* hint, const alch_buf* in, alch_buf* out, size_t batch, const uint64_t* s_pre,
+                                       unsigned flags) try {
+    if (!hint || !in || !out) return fail(ALCH_E_INVALID, "alch_ct_key_switch_quad: null argument");
+    alch_ring* r = hint->ring;
+    if (in->ring != r || out->ring != r) return fail(ALCH_E_INVALID, "alch_ct_key_switch_quad: the buffers must belong to the hint's ring");
+    if (batch > in->n_elems / 3 || !pairs_ok(batch, out->n_elems))
+        return fail(ALCH_E_INVALID, "alch_ct_key_switch_quad: in must hold 3*batch ring elements, out 2*batch");
+    if (flags & ~(unsigned)(ALCH_POW_IN | ALCH_POW_OUT)) return fail(ALCH_E_INVALID, "alch_ct_key_switch_quad: unknown flag");
+    if (out == in || bytes_overlap(out->dptr, 2 * batch * elem_bytes(r), in->dptr, 3 * batch * elem_bytes(r)))
+        return fail(ALCH_E_INVALID, "alch_ct_key_switch_quad: out must not alias the input");
+    if (!r->has_crt) return fail(ALCH_E_NO_CRT, "alch_ct_key_switch_quad: this ring has no CRT basis");
+    if (batch == 0) return ALCH_OK;
+    BIND(r);
+    return ALCH_BY_WORD(r, do_key_switch_quad, r, hint, in->dptr, out->dptr, batch, s_pre, flags);
+} catch (...) { return abi_catch(); }
+
 // ---- the complete mul_: (*) . modSwitch up . keySwitchQuadCirc . modSwitch down -------------------------------
 // Constants of the closing modSwitch that drops the first ddn limbs of `r` (outermost first): q_u^-1 mod q_t for the
 // limb-at-a-time form, prod_{w >= u} q_w^-1 mod q_t for the forms that keep the surviving limbs in the CRT basis.
@@ -2890,23 +3069,24 @@ static int do_mul_full(alch_ring* rh, alch_ring* rin, alch_ring* rout, const alc
 // CRT-resident form (general index, option rs_lin): the kept limbs stay in the CRT basis (k_gen_rescale_drop / k_gen_rescale_keep):
 // ddn inverse + (L - ddn) forward transforms per component instead of L + (L - ddn).  res: ddn * n words of scratch per element.
 template <typename W>
-static int rescale_down_crt(alch_ring* r, int ddn, const void* in, void* res, void* out, size_t elems, bool dec_c0, bool pow_out) {
+static int rescale_down_crt(alch_ring* r, int ddn, const void* in, void* res, void* out, size_t elems, bool dec_c0, bool pow_out,
+                            size_t per = 2) {
     DropTab<W> dt;
     fill_drop_tab<W>(r, ddn, dt);
     const hipError_t e = gen_rescale_lin_dispatch(dev_ring<W>(r), gen_dev<W>(r), reinterpret_cast<const W*>(in), reinterpret_cast<W*>(res),
-                                                  reinterpret_cast<W*>(out), dt, dec_c0 ? 1 : 0, elems, r->stream, pow_out);
+                                                  reinterpret_cast<W*>(out), dt, dec_c0 ? (int)per : 0, elems, r->stream, pow_out);   // c0 = every per-th element
     return e == hipSuccess ? ALCH_OK : fail(ALCH_E_HIP, std::string("rescale launch: ") + hipGetErrorString(e));
 }
 
-// Limb-at-a-time form.  cur: per * now elements of r on the Pow basis; c0 of every pair goes onto the Dec basis first for a general index
-// (dec_c0, per = 2: rescaleDec).  The limbs are dropped outermost first through ping / pong (per * now elements each), the last step
+// Limb-at-a-time form.  cur: per * now elements of r on the Pow basis; c0 of every ciphertext (every per-th element) goes onto the Dec
+// basis first for a general index (dec_c0, per = 2 or 3: rescaleDec).  The limbs are dropped outermost first through ping / pong (per * now elements each), the last step
 // writes elements per * first .. of `out`; then back to the CRT basis on ring_out (same device tables as r's: queued on r's stream).
 template <typename W>
 static int rescale_down_limbs(alch_ring* r, alch_ring* rout, char* cur, char* ping, char* pong, void* out, size_t first, size_t now,
                               size_t per, bool dec_c0, bool pow_out) {
     const int ddn = r->L - rout->L;
     int rc;
-    if (dec_c0 && (rc = do_columns<W>(r, GEN_LINV, cur, 0, now, 2)) != ALCH_OK) return rc;
+    if (dec_c0 && (rc = do_columns<W>(r, GEN_LINV, cur, 0, now, per)) != ALCH_OK) return rc;
     for (int u = 0; u < ddn; ++u) {
         char* nxt = (u + 1 == ddn) ? reinterpret_cast<char*>(out) + first * per * elem_bytes(rout) : ((u & 1) ? pong : ping);
         const DevRing<W> rs = suffix_view<W>(r, u);
@@ -2916,7 +3096,7 @@ static int rescale_down_limbs(alch_ring* r, alch_ring* rout, char* cur, char* pi
         HIP_TRY(hipGetLastError());
         cur = nxt;
     }
-    if (dec_c0 && (rc = do_columns<W>(rout, GEN_L, out, 2 * first, now, 2, r->stream)) != ALCH_OK) return rc;
+    if (dec_c0 && (rc = do_columns<W>(rout, GEN_L, out, per * first, now, per, r->stream)) != ALCH_OK) return rc;
     if (!pow_out && (rc = do_crt<W>(rout, out, per * first, per * now, false, nullptr, r->stream)) != ALCH_OK) return rc;
     return ALCH_OK;
 }
@@ -3473,7 +3653,8 @@ extern "C" int alch_ct_tunnel(const alch_tunnel* t, const alch_buf* in, alch_buf
 // ------------------------------------------------------------------------------------------------------
 // SymmSHE modSwitch on batches of linear ciphertexts (Eval.hs:130; PT2CT.hs:177,224-229)
 // ------------------------------------------------------------------------------------------------------
-// per = 2: linear ciphertexts (c0 rescaled on the decoding basis, c1 on the powerful basis); per = 1: `batch` single ring elements, all on
+// per = 2: linear ciphertexts (c0 rescaled on the decoding basis, c1 on the powerful basis); per = 3: quadratic ciphertexts (c0, c1, c2),
+// c2 on the powerful basis like c1 (alch_ct_mod_switch_deg); per = 1: `batch` single ring elements, all on
 // the powerful basis (the c2 of a quadratic ciphertext: SymmSHE's modSwitch rescales every coefficient above c0 with rescalePow)
 template <typename W>
 static int do_mod_switch(alch_ring* rin, alch_ring* rout, const void* in, void* out, size_t batch, unsigned flags, int per) {
@@ -3494,7 +3675,7 @@ static int do_mod_switch(alch_ring* rin, alch_ring* rout, const void* in, void* 
     // down: Pow basis (c0 on the Dec basis for a general index), one limb at a time, outermost first
     const int L = rin->L, ddn = L - rout->L;
     const size_t eb = elem_bytes(rin);
-    const bool dec_c0 = per == 2 && rin->gen && rin->gh.rad > 1;
+    const bool dec_c0 = per >= 2 && rin->gen && rin->gh.rad > 1;
     if (rin->gen && rin->opts.rs_lin && ddn <= MAXDROP && !(flags & ALCH_POW_IN)) {
         // kept limbs stay in the CRT basis
         const size_t per_b = P * (size_t)ddn * n * sizeof(W);
@@ -3505,7 +3686,7 @@ static int do_mod_switch(alch_ring* rin, alch_ring* rout, const void* in, void* 
             const size_t now = std::min(chunk, batch - done);
             if ((rc = rescale_down_crt<W>(rin, ddn, reinterpret_cast<const char*>(in) + done * P * eb, rin->ws_full,
                                           reinterpret_cast<char*>(out) + done * P * elem_bytes(rout), P * now, dec_c0,
-                                          (flags & ALCH_POW_OUT) != 0)) != ALCH_OK) return rc;
+                                          (flags & ALCH_POW_OUT) != 0, P)) != ALCH_OK) return rc;
         }
         return ALCH_OK;
     }
@@ -3549,6 +3730,31 @@ extern "C" int alch_ct_mod_switch(const alch_buf* in, alch_buf* out, size_t batc
     int rc;
     if ((rc = ext_order(rw, ro, true)) != ALCH_OK) return rc;
     if ((rc = ALCH_BY_WORD(rin, do_mod_switch, rin, rout, in->dptr, out->dptr, batch, flags)) != ALCH_OK) return rc;
+    return ext_order(rw, ro, false);
+} catch (...) { return abi_catch(); }
+
+// The same for ciphertexts of degree 1 or 2 (within ABI 1.8): degree 1 is alch_ct_mod_switch word for word, degree 2 switches the
+// quadratic ciphertext between (*) and keySwitchQuadCirc (PT2CT.hs:177 inner modSwitch_), c0 on the decoding basis, c1 and c2 on the powerful.
+extern "C" int alch_ct_mod_switch_deg(const alch_buf* in, alch_buf* out, size_t batch, int degree, unsigned flags) try {
+    if (!in || !out) return fail(ALCH_E_INVALID, "alch_ct_mod_switch_deg: null buffer");
+    alch_ring* rin = in->ring;
+    alch_ring* rout = out->ring;
+    if (flags & ~(unsigned)(ALCH_POW_IN | ALCH_POW_OUT)) return fail(ALCH_E_INVALID, "alch_ct_mod_switch_deg: unknown flag");
+    if (degree != 1 && degree != 2) return fail(ALCH_E_INVALID, "alch_ct_mod_switch_deg: degree must be 1 or 2");
+    const bool up = rout->L > rin->L;
+    if (rin->L == rout->L || !(up ? is_suffix_ring(rin, rout) : is_suffix_ring(rout, rin)))
+        return fail(ALCH_E_INVALID, "alch_ct_mod_switch_deg: the smaller ring's moduli must be the last limbs of the bigger ring's (same index and word size)");
+    const size_t per = (size_t)degree + 1;
+    if (batch > in->n_elems / per || batch > out->n_elems / per)
+        return fail(ALCH_E_INVALID, "alch_ct_mod_switch_deg: buffers must hold (degree + 1) * batch ring elements");
+    if (!rin->has_crt || !rout->has_crt) return fail(ALCH_E_NO_CRT, "alch_ct_mod_switch_deg: modSwitch runs on rings with a CRT basis");
+    if (batch == 0) return ALCH_OK;
+    alch_ring* rw = up ? rout : rin;                          // the ring whose stream carries the work
+    alch_ring* ro = up ? rin : rout;
+    BIND(rw);
+    int rc;
+    if ((rc = ext_order(rw, ro, true)) != ALCH_OK) return rc;
+    if ((rc = ALCH_BY_WORD(rin, do_mod_switch, rin, rout, in->dptr, out->dptr, batch, flags, (int)per)) != ALCH_OK) return rc;
     return ext_order(rw, ro, false);
 } catch (...) { return abi_catch(); }
 
@@ -3605,10 +3811,6 @@ extern "C" int alch_buf_rescale_add0(const alch_buf* src, alch_buf* dst, size_t 
 // ------------------------------------------------------------------------------------------------------
 // decrypt and errorRate_ on resident batches (PT2CT.hs:91-99, Eval.hs:150-160): c(s) on the decoding basis, centred lift
 // ------------------------------------------------------------------------------------------------------
-static bool bytes_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const char *x = reinterpret_cast<const char*>(a), *y = reinterpret_cast<const char*>(b);
-    return x < y + nb && y < x + na;
-}
 
 // Everything alch_buf_lift's kernel needs about (source ring, destination modulus).  rd == null: no residues wanted.
 template <typename W>

@@ -1001,7 +1001,7 @@ __global__ void __launch_bounds__(NT, 4) k_gen_rescale_drop(DevRing<W> R, GenDev
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     W* lds = reinterpret_cast<W*>(smem);
     const int L = R.L;
-    const size_t e = blockIdx.x / (unsigned)ddn;             // element = 2 ct + component
+    const size_t e = blockIdx.x / (unsigned)ddn;             // element = dec_c0 * ct + component (dec_c0: 0, or elements per ciphertext)
     const int u = (int)(blockIdx.x % (unsigned)ddn);
     const u32 n = G.n;
     const W* src = in + (e * (size_t)L + u) * (size_t)n;
@@ -1014,7 +1014,7 @@ __global__ void __launch_bounds__(NT, 4) k_gen_rescale_drop(DevRing<W> R, GenDev
     else for (u32 i = threadIdx.x; i < n; i += NT) lds[i] = src[i];
     lds_barrier();
     gen_transform<W, true, NT>(lds, G, u, q, qni);
-    if (dec_c0 && (e & 1) == 0) {                            // c0 is rescaled on the Dec basis
+    if (dec_c0 && e % (size_t)dec_c0 == 0) {                            // c0 is rescaled on the Dec basis
         ColArith<W, false> A{q, qni, R.mod[u].r2, 0};
         gen_columns_lds<W, false, GEN_LINV, NT>(lds, G, A, 0u);
     }
@@ -1092,7 +1092,7 @@ __global__ void __launch_bounds__(NT, 4) k_gen_rescale_keep(DevRing<W> R, GenDev
         }
     }
     lds_barrier();
-    if (dec_c0 && (e & 1) == 0) {                            // Dec -> Pow
+    if (dec_c0 && e % (size_t)dec_c0 == 0) {                            // Dec -> Pow
         ColArith<W, false> A{q, qni, R.mod[t].r2, 0};
         gen_columns_lds<W, false, GEN_L, NT>(lds, G, A, 0u);
     }
@@ -1142,7 +1142,7 @@ __global__ void __launch_bounds__(NT, 4) k_gen_rescale_keep_pow(DevRing<W> R, Ge
     else for (u32 i = threadIdx.x; i < n; i += NT) lds[i] = x[i];
     lds_barrier();
     gen_transform<W, true, NT>(lds, G, t, q, qni);
-    const bool dec = dec_c0 && (e & 1) == 0;
+    const bool dec = dec_c0 && e % (size_t)dec_c0 == 0;
     ColArith<W, false> A{q, qni, R.mod[t].r2, 0};
     if (dec) gen_columns_lds<W, false, GEN_LINV, NT>(lds, G, A, 0u);
     const W scCt = csub(mont_mul_lazy(G.iscale_m[t], D.comb_m[0][t], q, qni), q);      // crtInv's closing scalar times C_t (Montgomery form)

@@ -15,6 +15,9 @@
 //   genSK, ksQuadCircHint, encrypt, decrypt                (KeysHints.hs:93-96,101-113; PT2CT.hs:84-99)
 //   mulRelinBatch  the fused device path for PT2CT's  keySwitchQuad_ hint $: (x *: y)  (PT2CT.hs:172-177)
 //   mulFullBatch   the fused device path for the whole mul_ with the longer hint modulus (PT2CT.hs:139,160-177)
+//   ctMulBatch, keySwitchQuadBatch, modSwitchDegBatch   the same mul_ one SHE operation at a time on device batches (alch_ct_mul,
+//                  alch_ct_key_switch_quad, alch_ct_mod_switch_deg): the quadratic ciphertext exists, so errorRatesBatch
+//                  (alch_ct_decrypt_lift) can log a rate after every step, as the reference's ErrorRateWriter does
 //
 // Everything numeric goes through the C ABI (device kernels); this file only sequences calls and keeps the
 // (enc, k, l) metadata.  Errors surface as std::runtime_error carrying alch_last_error().
@@ -458,6 +461,127 @@ inline std::vector<CT> mulFullBatch(const Ring& rin, const Ring& rh, const Ring&
     }
     alch_hint_free(dh);
     alch_buf_free(ba); alch_buf_free(bb); alch_buf_free(bo); alch_buf_free(bh);
+    return out;
+}
+
+// ---- mul_ one SHE operation at a time on device batches -----------------------------------------------------------
+// Thin wrappers: upload, ONE call, download.  A caller that chains steps on the device passes `resident`: the result
+// buffer is then handed over too (free it with alch_buf_free) and can be fed to the next entry point directly.
+inline alch_buf* uploadCTs(const Ring& r, const std::vector<CT>& cts, size_t per) {
+    alch_buf* b = nullptr;
+    check(alch_buf_alloc(r.handle(), per * cts.size(), &b), "alch_buf_alloc");
+    for (size_t i = 0; i < cts.size(); ++i) {
+        if (cts[i].c.size() != per) { alch_buf_free(b); throw std::runtime_error("uploadCTs: ciphertexts of another degree"); }
+        for (size_t c = 0; c < per; ++c) check(alch_buf_upload(b, per * i + c, 1, cts[i].c[c].adviseCRT().data().data()), "alch_buf_upload");
+    }
+    return b;
+}
+
+inline std::vector<CT> downloadCTs(const Ring& r, const alch_buf* b, size_t B, size_t per, Basis basis, const CT& meta) {
+    std::vector<CT> out;
+    for (size_t i = 0; i < B; ++i) {
+        CT o{meta.enc, meta.k, meta.l, meta.p, std::vector<Cyc>(per, Cyc(r, basis))};
+        for (size_t c = 0; c < per; ++c) check(alch_buf_download(b, per * i + c, 1, o.c[c].data().data()), "alch_buf_download");
+        out.push_back(std::move(o));
+    }
+    return out;
+}
+
+// SymmSHE (*) on batches of linear ciphertexts (Eval.hs:65-67): quadratic LSD ciphertexts, k = k1+k2+1, l = l1*l2; the operands'
+// toLSD scalars ride on the tensor product.  Inputs must share (enc, k, l).
+inline std::vector<CT> ctMulBatch(const Ring& r, const std::vector<CT>& xs, const std::vector<CT>& ys, alch_buf** resident = nullptr) {
+    const size_t B = xs.size();
+    if (B == 0 || ys.size() != B) throw std::runtime_error("ctMulBatch: batch mismatch");
+    std::vector<uint64_t> s(r.L(), 1);
+    uint64_t lx = xs[0].l, ly = ys[0].l;
+    const uint64_t p = xs[0].p;
+    const uint64_t negq = (p - qprod_mod(r, p)) % p;
+    auto fold = [&](Encoding enc, uint64_t& l) {               // toLSD
+        if (enc == Encoding::MSD) {
+            for (int j = 0; j < r.L(); ++j) s[j] = mulmod(s[j], p % r.qs()[j], r.qs()[j]);
+            l = mulmod(l, invmod(negq, p), p);
+        }
+    };
+    fold(xs[0].enc, lx);
+    fold(ys[0].enc, ly);
+    alch_buf *ba = uploadCTs(r, xs, 2), *bb = uploadCTs(r, ys, 2), *bo = nullptr;
+    check(alch_buf_alloc(r.handle(), 3 * B, &bo), "alch_buf_alloc");
+    check(alch_ct_mul(r.handle(), ba, bb, bo, B, s.data(), 0), "alch_ct_mul");
+    std::vector<CT> out = downloadCTs(r, bo, B, 3, Basis::CRT, CT{Encoding::LSD, xs[0].k + ys[0].k + 1, mulmod(lx, ly, p), p, {}});
+    alch_buf_free(ba); alch_buf_free(bb);
+    if (resident) *resident = bo; else alch_buf_free(bo);
+    return out;
+}
+
+// keySwitchQuadCirc hint (Eval.hs:133) on batches of quadratic ciphertexts of the hint's ring: toMSD's scalar is the call's s_pre.
+inline std::vector<CT> keySwitchQuadBatch(const Ring& r, const KSQuadCircHint& hint, const std::vector<CT>& cts,
+                                          alch_buf** resident = nullptr) {
+    const size_t B = cts.size();
+    if (B == 0) throw std::runtime_error("keySwitchQuadBatch: empty batch");
+    CT meta{Encoding::MSD, cts[0].k, cts[0].l, cts[0].p, {}};
+    std::vector<uint64_t> s(r.L(), 1);
+    if (cts[0].enc == Encoding::LSD) {                         // toMSD
+        const uint64_t p = cts[0].p;
+        for (int j = 0; j < r.L(); ++j) s[j] = invmod(p % r.qs()[j], r.qs()[j]);
+        meta.l = mulmod(meta.l, (p - qprod_mod(r, p)) % p, p);
+    }
+    alch_buf *bi = uploadCTs(r, cts, 3), *bo = nullptr, *bh = nullptr;
+    alch_hint* dh = nullptr;
+    check(alch_buf_alloc(r.handle(), 2 * B, &bo), "alch_buf_alloc");
+    check(alch_buf_alloc(r.handle(), 2 * (size_t)r.L(), &bh), "alch_buf_alloc");
+    for (int i = 0; i < r.L(); ++i) {
+        check(alch_buf_upload(bh, 2 * i, 1, hint.h[i].first.adviseCRT().data().data()), "alch_buf_upload");
+        check(alch_buf_upload(bh, 2 * i + 1, 1, hint.h[i].second.adviseCRT().data().data()), "alch_buf_upload");
+    }
+    check(alch_hint_from_buf(r.handle(), ALCH_GAD_TRIV, bh, &dh), "alch_hint_from_buf");
+    check(alch_ct_key_switch_quad(dh, bi, bo, B, s.data(), 0), "alch_ct_key_switch_quad");
+    std::vector<CT> out = downloadCTs(r, bo, B, 2, Basis::CRT, meta);
+    alch_hint_free(dh);
+    alch_buf_free(bi); alch_buf_free(bh);
+    if (resident) *resident = bo; else alch_buf_free(bo);
+    return out;
+}
+
+// SymmSHE modSwitch (Eval.hs:130) on batches of MSD ciphertexts of one degree (1 or 2) between two rings whose moduli nest: up leaves
+// the CRT basis, down returns the Pow basis (what Lol's rescale leaves).
+inline std::vector<CT> modSwitchDegBatch(const Ring& src, const Ring& dst, const std::vector<CT>& cts_, alch_buf** resident = nullptr) {
+    const size_t B = cts_.size();
+    if (B == 0) throw std::runtime_error("modSwitchDegBatch: empty batch");
+    std::vector<CT> cts;
+    for (const CT& c : cts_) cts.push_back(toMSD(c));
+    const size_t per = cts[0].c.size();
+    if (per != 2 && per != 3) throw std::runtime_error("modSwitchDegBatch: ciphertext degree must be 1 or 2");
+    const bool down = dst.L() < src.L();
+    alch_buf *bi = uploadCTs(src, cts, per), *bo = nullptr;
+    check(alch_buf_alloc(dst.handle(), per * B, &bo), "alch_buf_alloc");
+    check(alch_ct_mod_switch_deg(bi, bo, B, (int)per - 1, down ? ALCH_POW_OUT : 0), "alch_ct_mod_switch_deg");
+    std::vector<CT> out = downloadCTs(dst, bo, B, per, down ? Basis::Pow : Basis::CRT, CT{Encoding::MSD, cts[0].k, cts[0].l, cts[0].p, {}});
+    alch_buf_free(bi);
+    if (resident) *resident = bo; else alch_buf_free(bo);
+    return out;
+}
+
+// errorRate_ of every ciphertext of a batch as the ErrorRateWriter logs it (Eval.hs:150-160): max |liftDec(c(s))| / Q of the LSD
+// form, one alch_ct_decrypt_lift call; the exact digit vector is rounded once.  Linear or quadratic ciphertexts.
+inline std::vector<double> errorRatesBatch(const Ring& r, const SK& sk, const std::vector<CT>& cts) {
+    const size_t B = cts.size();
+    if (B == 0) return {};
+    const size_t per = cts[0].c.size();
+    std::vector<uint64_t> s(r.L(), 1);
+    if (cts[0].enc == Encoding::MSD) for (int j = 0; j < r.L(); ++j) s[j] = cts[0].p % r.qs()[j];     // toLSD
+    alch_buf *bi = uploadCTs(r, cts, per), *bs = nullptr;
+    check(alch_buf_alloc(r.handle(), 1, &bs), "alch_buf_alloc");
+    check(alch_buf_upload(bs, 0, 1, Cyc::fromIntegers(r, sk.s).adviseCRT().data().data()), "alch_buf_upload");
+    std::vector<uint64_t> digits(B * (size_t)r.L());
+    check(alch_ct_decrypt_lift(bi, B, (int)per - 1, bs, 0, s.data(), nullptr, 0, 1, digits.data(), 0), "alch_ct_decrypt_lift");
+    alch_buf_free(bi); alch_buf_free(bs);
+    std::vector<double> out(B);
+    for (size_t i = 0; i < B; ++i) {
+        long double x = 0, Q = 1;
+        for (int j = r.L(); j-- > 0;) x = x * (long double)r.qs()[j] + (long double)digits[i * r.L() + j];
+        for (uint64_t q : r.qs()) Q *= (long double)q;
+        out[i] = (double)(x / Q);
+    }
     return out;
 }
 

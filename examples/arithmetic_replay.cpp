@@ -8,8 +8,12 @@
 //                 keySwitchQuadCirc hint ;  modSwitch (drop the outer limb).
 // Runs the per-op path and the fused batch path, checks they agree bit for bit, decrypts and compares with
 // the plaintext evaluation, and prints PASS / FAIL like the reference (examples/Arithmetic.hs:73-75).
+// With --steps the product s * y additionally runs one SHE operation at a time on the device (alch_ct_mul ->
+// alch_ct_key_switch_quad -> alch_ct_mod_switch_deg), is checked bit for bit against the fused batch path, and one line per step
+// gives its error rate, as the reference prints them (examples/Arithmetic.hs:67, writeErrorRates).
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include "../alchemy_amd/host/symmshe.hpp"
 
@@ -29,7 +33,12 @@ static std::vector<uint64_t> ptMul(const std::vector<uint64_t>& a, const std::ve
 }
 
 int main(int argc, char** argv) {
-    const uint32_t m = argc > 1 ? (uint32_t)atoi(argv[1]) : 512;
+    uint32_t m = 512;
+    bool steps = false;
+    for (int i = 1; i < argc; ++i) {
+        if (!strcmp(argv[i], "--steps")) steps = true;
+        else m = (uint32_t)atoi(argv[i]);
+    }
     const uint64_t p = 7;
     const size_t npt = 2;                                   // F4: phi = 2
     try {
@@ -76,11 +85,28 @@ int main(int argc, char** argv) {
         for (int c = 0; c < 2; ++c) same3 = same3 && full[0].c[c].advisePow().data() == result3.c[c].advisePow().data();
         printf("fused full mul_ (2 -> 3 -> 1 limbs) == per-op path: %s\n", same3 ? "yes" : "NO");
 
+        // --steps: mul_, keySwitchQuad_ and modSwitch_ as three device calls, a rate after each
+        bool same_steps = true;
+        if (steps) {
+            std::vector<CT> quad = ctMulBatch(ring2, {s}, {arg2});
+            printf("mul_ error rate: %.6e\n", errorRatesBatch(ring2, sk, quad)[0]);
+            std::vector<CT> lin = keySwitchQuadBatch(ring2, hint, quad);
+            printf("keySwitchQuad_ error rate: %.6e\n", errorRatesBatch(ring2, sk, lin)[0]);
+            std::vector<CT> low = modSwitchDegBatch(ring2, ring1, lin);
+            printf("modSwitch_ error rate: %.6e\n", errorRatesBatch(ring1, SK{sk.s, sk.r}, low)[0]);
+            same_steps = lin[0].l == fused[0].l && lin[0].k == fused[0].k && low[0].l == result2.l;
+            for (int c = 0; c < 2; ++c) {
+                same_steps = same_steps && lin[0].c[c].adviseCRT().data() == fused[0].c[c].adviseCRT().data();
+                same_steps = same_steps && low[0].c[c].advisePow().data() == result2.c[c].advisePow().data();
+            }
+            printf("step path == fused path: %s\n", same_steps ? "yes" : "NO");
+        }
+
         SK sk1{sk.s, sk.r};
         std::vector<uint64_t> dec = decrypt(sk1, result, npt), dec2 = decrypt(sk1, result2, npt);
         printf("Decrypted evaluation result: [%llu, %llu]\n", (unsigned long long)dec[0], (unsigned long long)dec[1]);
         std::vector<uint64_t> dec3 = decrypt(sk1, full[0], npt);
-        const bool ok = same && same3 && dec == ptresult && dec2 == ptresult && dec3 == ptresult;
+        const bool ok = same && same3 && same_steps && dec == ptresult && dec2 == ptresult && dec3 == ptresult;
         printf("%s\n", ok ? "PASS" : "FAIL");
         return ok ? 0 : 1;
     } catch (const std::exception& e) {

@@ -134,3 +134,7 @@ foreign import ccall safe   "alch_ct_decrypt_lift"     c_ctDecryptLift   :: Ptr 
 -- the hot path: keySwitchQuadCirc hint (a * b), and PT2CT's whole mul_
 foreign import ccall safe   "alch_ct_mul_relin"        c_ctMulRelin      :: Ptr AlchRing -> Ptr AlchHint -> Ptr AlchBuf -> Ptr AlchBuf -> Ptr AlchBuf -> CSize -> Ptr Word64 -> CUInt -> IO CInt
 foreign import ccall safe   "alch_ct_mul_full"         c_ctMulFull       :: Ptr AlchHint -> Ptr AlchBuf -> Ptr AlchBuf -> Ptr AlchBuf -> CSize -> Ptr Word64 -> CUInt -> IO CInt
+-- mul_ one SHE operation at a time (added within library version 1.8): (*), keySwitchQuadCirc and modSwitch of degree 1 or 2 on resident batches
+foreign import ccall safe   "alch_ct_mul"              c_ctMul           :: Ptr AlchRing -> Ptr AlchBuf -> Ptr AlchBuf -> Ptr AlchBuf -> CSize -> Ptr Word64 -> CUInt -> IO CInt
+foreign import ccall safe   "alch_ct_key_switch_quad"  c_ctKeySwitchQuad :: Ptr AlchHint -> Ptr AlchBuf -> Ptr AlchBuf -> CSize -> Ptr Word64 -> CUInt -> IO CInt
+foreign import ccall safe   "alch_ct_mod_switch_deg"   c_ctModSwitchDeg  :: Ptr AlchBuf -> Ptr AlchBuf -> CSize -> CInt -> CUInt -> IO CInt

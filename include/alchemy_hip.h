@@ -81,7 +81,9 @@ typedef struct alch_tunnel alch_tunnel;
 #define ALCH_GAD_BASE2 1           /* BaseBGad 2: sum_i ceil(log2 q_i) digits; unfused device path */
 
 const char *alch_last_error(void);
-/* Library/ABI version: (major<<16)|minor; the minor number goes up with every added capability (1.7: tunnels between two-power rings; 1.8: decrypt / error rates on resident batches). */
+/* Library/ABI version: (major<<16)|minor; the minor number goes up with every added capability (1.7: tunnels between two-power rings; 1.8: decrypt / error rates on resident batches).).
+ * The step entry points of mul_ (alch_ct_mul, alch_ct_key_switch_quad, alch_ct_mod_switch_deg) were added WITHIN 1.8 -- the number did
+ * not move; a host that wants them probes for the symbols (dlsym / ctypes hasattr). */
 uint32_t alch_version(void);
 
 /* ---- ring context ------------------------------------------------------------------------------
@@ -416,6 +418,38 @@ int alch_ct_tunnel(const alch_tunnel *t, const alch_buf *in, alch_buf *out, size
  *   out has fewer limbs: Rescale (a, b) -> b per dropped limb (any number), c0 rescaled on the Dec basis and c1 on the Pow basis
  *   (Lol: rescaleDec / rescalePow); CRT basis in and out unless ALCH_POW_IN / ALCH_POW_OUT.  The input is not modified. */
 int alch_ct_mod_switch(const alch_buf *in, alch_buf *out, size_t batch, unsigned flags);
+
+/* ---- mul_ one SHE operation at a time on resident ciphertext batches (added within 1.8; probe for the symbols) ------------
+ * PT2CT emits a multiplication as four object-language operations, modSwitch_ . keySwitchQuad_ hint . modSwitch_ $ x *: y
+ * (PT2CT.hs:160-177), E binds each on its own (Eval.hs:65-67,130,133) and the ErrorRateWriter logs a rate after each
+ * (ErrorRateWriter.hs:122,194,197).  These three entry points, with alch_ct_mod_switch, are those four operations: the quadratic
+ * ciphertext exists in a caller's buffer and alch_ct_decrypt_lift (degree 2) can look at it.  They are the inspection path -- composed
+ * from element-wise kernels and batched transforms at every size; alch_ct_mul_relin / alch_ct_mul_full stay the fast one and give the
+ * same words.
+ * A quadratic ciphertext b is elements (3b, 3b+1, 3b+2) = (c0, c1, c2): the layout alch_ct_error_term documents for degree = 2.
+ * CRT basis in and out unless ALCH_POW_IN / ALCH_POW_OUT.  batch = 0: ALCH_OK, nothing done.  The input is never modified and `out`
+ * must not alias it.  Statuses, in this order: ALCH_E_INVALID (null handle; handles of different rings; buffer too small; unknown
+ * flag; degree not 1 or 2; the smaller ring's moduli not the last limbs of the bigger ring's), ALCH_E_NO_CRT (a ring created with
+ * alch_ring_create_nocrt), device errors last. */
+/* SymmSHE (*) on linear ciphertexts (Eval.hs:65-67): out[b] = s_pre * mulG(a[b] (x) b[b]),
+ * (c0,c1,c2) = (a0 b0, a0 b1 + a1 b0, a1 b1), mulG on every component (identity on a two-power index).
+ * s_pre[j] = product of both operands' toLSD scalars (NULL = 1).  a, b: 2*batch elements, out: 3*batch, one ring. */
+int alch_ct_mul(alch_ring *ring, const alch_buf *a, const alch_buf *b, alch_buf *out, size_t batch,
+                const uint64_t *s_pre, unsigned flags);
+
+/* keySwitchQuadCirc hint (Eval.hs:133) on resident quadratic ciphertexts of the hint's ring:
+ * out[b] = s_pre*(c0, c1) + sum_d crt(digit_d(s_pre*c2)) * hint_d.   s_pre = toMSD's per-limb scalar (NULL = 1).
+ * TrivGad and BaseBGad 2; every ring alch_ring_create accepts, the split sizes included.  in: 3*batch, out: 2*batch.
+ * The ring's launch options select among equivalent forms of the digit stage and never change a result. */
+int alch_ct_key_switch_quad(const alch_hint *hint, const alch_buf *in, alch_buf *out, size_t batch,
+                            const uint64_t *s_pre, unsigned flags);
+
+/* alch_ct_mod_switch for ciphertexts of degree 1 or 2 ((degree+1)*batch elements on both sides): up = every component
+ * times the added moduli; down = c0 rescaled on the decoding basis, every higher component on the powerful basis
+ * (SymmSHE modSwitch; for degree 2 the same recollection alch_ct_mul_full's BaseBGad-2 "fewer limbs" path already rests on).
+ * degree 1 gives alch_ct_mod_switch's results word for word.  Two rings on different streams are ordered as alch_ct_mod_switch
+ * orders them. */
+int alch_ct_mod_switch_deg(const alch_buf *in, alch_buf *out, size_t batch, int degree, unsigned flags);
 
 /* ---- decrypt and errorRate_ on resident ciphertext batches (since 1.8) -------------------------------------------------
  * SymmSHE decrypt (Crypto/Alchemy/Interpreter/PT2CT.hs:91-99) and errorTermUnrestricted as the ErrorRateWriter interpreter logs it
