@@ -38,6 +38,8 @@ SYMBOLS = [
     "alch_ring_share_stream", "alch_buf_copy", "alch_buf_tensor_op", "alch_buf_view", "alch_buf_ring", "alch_ring_device",
     "alch_ct_error_term", "alch_buf_lift", "alch_ct_decrypt_lift",
     "alch_ct_mul", "alch_ct_key_switch_quad", "alch_ct_mod_switch_deg",
+    "alch_pt_bound", "alch_pt_mul", "alch_pt_linear_create", "alch_pt_linear_free", "alch_pt_eval_lin", "alch_pt_rescale",
+    "alch_buf_add_bcast",
 ]
 
 
@@ -164,6 +166,13 @@ def load_library():
         "alch_ct_mul": [VP, VP, VP, VP, C.c_size_t, PU64, C.c_uint],
         "alch_ct_key_switch_quad": [VP, VP, VP, C.c_size_t, PU64, C.c_uint],
         "alch_ct_mod_switch_deg": [VP, VP, C.c_size_t, C.c_int, C.c_uint],
+        "alch_pt_bound": [C.c_uint32, C.c_uint64, C.c_uint32, PU64, PU64],
+        "alch_pt_mul": [VP, VP, VP, VP, C.c_size_t, C.c_uint],
+        "alch_pt_linear_create": [VP, VP, C.c_uint32, C.POINTER(VP)],
+        "alch_pt_linear_free": [VP],
+        "alch_pt_eval_lin": [VP, VP, VP, C.c_size_t, C.c_uint],
+        "alch_pt_rescale": [VP, VP, C.c_size_t],
+        "alch_buf_add_bcast": [VP, VP, VP, C.c_size_t, C.c_size_t],
     }
     for name, args in sig.items():
         fn = getattr(l, name)

@@ -21,6 +21,7 @@
 #include "kernels_ntt.hpp"
 #include "ring_host.hpp"
 #include "gen_host.hpp"
+#include "plain_host.hpp"
 
 using namespace alch;
 
@@ -1213,6 +1214,7 @@ __global__ void k_checksum(const W* data, size_t words, u64* sum, u64 w0) {
 }
 
 #include "kernel_lift.hpp"
+#include "kernel_plain.hpp"
 
 static inline unsigned ew_grid(size_t items) {
     size_t g = (items + 255) / 256;
@@ -4007,6 +4009,305 @@ extern "C" int alch_ct_decrypt_lift(const alch_buf* in, size_t batch, int degree
     if (rc != ALCH_OK) return rc;
     if (rd && (rc = ext_order(r, rd, false)) != ALCH_OK) return rc;
     return maxd_fetch(r, max_digits, batch);
+} catch (...) { return abi_catch(); }
+
+// ------------------------------------------------------------------------------------------------------
+// plaintext-side mul_, div2_ and linearCyc_ on resident batches (Eval.hs:65-67, 72-88, 136-148): kernel_plain.hpp
+// ------------------------------------------------------------------------------------------------------
+// A linear function R_p -> S_p, kept as its values on the (folded) relative basis, lifted, in the CRT basis of the lifting ring.
+struct alch_ptlin {
+    alch_ring* lift;                           // lifting ring of index s
+    u32 m_r, n_r, d_rel;
+    u64 p;
+    void* ys = nullptr;                        // device: [d_rel][L][n_s], CRT basis, Montgomery form
+    int32_t* table = nullptr;                  // device: [d_rel][n_s] source positions in the index-r element, -1 = zero
+};
+
+// The exactness bound of include/alchemy_hip.h: terms * phi(m) * 2^(odd primes of m) * floor(p/2)^2.
+static int pt_bound(uint32_t m, uint64_t p, uint64_t terms, unsigned __int128* out) {
+    if (m < 1 || p < 2 || p >= ((u64)1 << 31)) return fail(ALCH_E_INVALID, "plaintext bound: the modulus must satisfy 2 <= p < 2^31");
+    if (terms < 1 || terms > 65536) return fail(ALCH_E_INVALID, "plaintext bound: 1 .. 65536 terms");
+    if (!pt_bound_value(m, p, terms, out)) return fail(ALCH_E_INVALID, "plaintext bound: bad argument");      // plain_host.hpp
+    return ALCH_OK;
+}
+
+extern "C" int alch_pt_bound(uint32_t m, uint64_t p, uint32_t terms, uint64_t* lo, uint64_t* hi) try {
+    if (!lo || !hi) return fail(ALCH_E_INVALID, "alch_pt_bound: null argument");
+    unsigned __int128 b = 0;
+    if (int rc = pt_bound(m, p, terms, &b)) return rc;
+    *lo = (uint64_t)b;
+    *hi = (uint64_t)(b >> 64);
+    return ALCH_OK;
+} catch (...) { return abi_catch(); }
+
+// Q / 2 > bound for the lifting ring's Q = prod q_j (Q is odd: Q > 2 bound).
+static int pt_check_q(const std::string& who, const alch_ring* lift, uint64_t p, uint64_t terms) {
+    unsigned __int128 b = 0;
+    if (int rc = pt_bound(lift->m, p, terms, &b)) return rc;
+    if (pt_q_exceeds(lift->q, lift->L, b)) return ALCH_OK;
+    return fail(ALCH_E_INVALID, who + ": the lifting ring is too small -- Q/2 must exceed terms * phi(m) * 2^(odd primes of m) * (p/2)^2 = 2^" +
+                                    std::to_string((int)std::ceil(std::log2((double)b + 1))) + " (terms = " + std::to_string(terms) + ")");
+}
+
+// A plaintext buffer's ring: one modulus 2 <= p < 2^31, 32-bit words.
+static int pt_check_zp(const std::string& who, const alch_ring* rp) {
+    if (rp->L != 1) return fail(ALCH_E_INVALID, who + ": a plaintext ring has exactly one modulus");
+    if (rp->zdom || rp->word != 4 || rp->q[0] < 2 || rp->q[0] >= ((u64)1 << 31)) return fail(ALCH_E_INVALID, who + ": the plaintext modulus must satisfy 2 <= p < 2^31");
+    return ALCH_OK;
+}
+static int pt_check_lift(const std::string& who, const alch_ring* lift, const alch_ring* rp) {
+    if (rp->m != lift->m || rp->n != lift->n) return fail(ALCH_E_INVALID, who + ": the lifting ring must have the plaintext ring's cyclotomic index");
+    if (rp->device != lift->device) return fail(ALCH_E_INVALID, who + ": the rings live on different devices");
+    if (!lift->has_crt) return fail(ALCH_E_NO_CRT, who + ": the lifting ring needs a CRT basis (a ring from alch_ring_create)");
+    return ALCH_OK;
+}
+
+template <typename W>
+static int pt_lift_in(alch_ring* lift, void* dst, const void* src, size_t count, u64 p) {
+    if (lift->n % 4 == 0)
+        hipLaunchKernelGGL((k_pt_lift_in<W, 4>), dim3(ew_grid(count * (size_t)lift->n / 4)), dim3(256), 0, lift->stream, dev_ring<W>(lift), (W*)dst, (const u32*)src, count, (u32)p);
+    else
+        hipLaunchKernelGGL((k_pt_lift_in<W, 1>), dim3(ew_grid(count * (size_t)lift->n)), dim3(256), 0, lift->stream, dev_ring<W>(lift), (W*)dst, (const u32*)src, count, (u32)p);
+    HIP_TRY(hipGetLastError());
+    return ALCH_OK;
+}
+
+// dst[e] = a[e] * b[e] over the lifting ring, in chunks that keep both lifted operands inside scratch_mib of the ring's scratch.
+template <typename W>
+static int do_pt_mul(alch_ring* lift, const alch_ring* rp, void* dst, const void* a, const void* b, size_t count) {
+    const size_t eb = elem_bytes(lift), zb = (size_t)lift->n * 4;
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(count, (lift->scratch_mib << 20) / (2 * eb)));
+    if (int rc = ensure_ws(&lift->ws_lift, &lift->ws_lift_bytes, 2 * chunk * eb)) return rc;
+    char* A = reinterpret_cast<char*>(lift->ws_lift);
+    for (size_t done = 0; done < count; done += chunk) {
+        const size_t now = std::min(chunk, count - done);
+        char* B = A + now * eb;                                       // both operands contiguous: one forward transform launch
+        if (int rc = pt_lift_in<W>(lift, A, reinterpret_cast<const char*>(a) + done * zb, now, rp->q[0])) return rc;
+        if (int rc = pt_lift_in<W>(lift, B, reinterpret_cast<const char*>(b) + done * zb, now, rp->q[0])) return rc;
+        if (int rc = do_crt<W>(lift, A, 0, 2 * now, false)) return rc;
+        if (int rc = do_pointwise<W, PW_MUL>(lift, A, A, B, now)) return rc;
+        if (int rc = do_crt<W>(lift, A, 0, now, true)) return rc;
+        if (int rc = launch_lift<W>(lift, rp, A, reinterpret_cast<char*>(dst) + done * zb, nullptr, now, 1)) return rc;
+    }
+    return ALCH_OK;
+}
+
+extern "C" int alch_pt_mul(alch_ring* lift, alch_buf* dst_zp, const alch_buf* a_zp, const alch_buf* b_zp, size_t count, unsigned flags) try {
+    if (!lift || !dst_zp || !a_zp || !b_zp) return fail(ALCH_E_INVALID, "alch_pt_mul: null argument");
+    BIND(lift);
+    alch_ring* rp = dst_zp->ring;
+    if (a_zp->ring != rp || b_zp->ring != rp) return fail(ALCH_E_INVALID, "alch_pt_mul: the three buffers must belong to one plaintext ring");
+    if (flags) return fail(ALCH_E_INVALID, "alch_pt_mul: no flag is defined");
+    if (int rc = pt_check_zp("alch_pt_mul", rp)) return rc;
+    if (int rc = pt_check_lift("alch_pt_mul", lift, rp)) return rc;
+    if (!range_ok(0, count, dst_zp->n_elems) || !range_ok(0, count, a_zp->n_elems) || !range_ok(0, count, b_zp->n_elems))
+        return fail(ALCH_E_INVALID, "alch_pt_mul: count out of bounds");
+    if (int rc = pt_check_q("alch_pt_mul", lift, rp->q[0], 1)) return rc;
+    if (count == 0) return ALCH_OK;
+    const size_t bytes = count * elem_bytes(rp);
+    // dst may be an operand (every chunk is lifted before its results are written); a shifted overlap is refused
+    if ((dst_zp->dptr != a_zp->dptr && bytes_overlap(dst_zp->dptr, bytes, a_zp->dptr, bytes)) ||
+        (dst_zp->dptr != b_zp->dptr && bytes_overlap(dst_zp->dptr, bytes, b_zp->dptr, bytes)))
+        return fail(ALCH_E_INVALID, "alch_pt_mul: the destination overlaps an operand without coinciding with it");
+    int rc;
+    if ((rc = ext_order(lift, rp, true)) != ALCH_OK) return rc;
+    if ((rc = ALCH_BY_WORD(lift, do_pt_mul, lift, rp, dst_zp->dptr, a_zp->dptr, b_zp->dptr, count)) != ALCH_OK) return rc;
+    return ext_order(lift, rp, false);
+} catch (...) { return abi_catch(); }
+
+extern "C" int alch_pt_linear_free(void* handle) try {
+    alch_ptlin* f = reinterpret_cast<alch_ptlin*>(handle);
+    if (!f) return ALCH_OK;
+    (void)hipSetDevice(f->lift->device);
+    (void)hipStreamSynchronize(f->lift->stream);
+    if (f->ys) (void)hipFree(f->ys);
+    if (f->table) (void)hipFree(f->table);
+    delete f;
+    return ALCH_OK;
+} catch (...) { return abi_catch(); }
+
+extern "C" int alch_pt_linear_create(alch_ring* lift_s, const alch_buf* ys_zp, uint32_t m_r, void** out) try {
+    if (!lift_s || !ys_zp || !out) return fail(ALCH_E_INVALID, "alch_pt_linear_create: null argument");
+    *out = nullptr;
+    BIND(lift_s);
+    alch_ring* rp = ys_zp->ring;
+    if (m_r < 1) return fail(ALCH_E_INVALID, "alch_pt_linear_create: bad source index");
+    if (int rc = pt_check_zp("alch_pt_linear_create", rp)) return rc;
+    if (int rc = pt_check_lift("alch_pt_linear_create", lift_s, rp)) return rc;
+    u32 e = m_r, t0 = lift_s->m;
+    while (t0) { const u32 t = e % t0; e = t0; t0 = t; }
+    GenHost ge, gr, gs;
+    if (!gen_factor(e, ge) || !gen_factor(m_r, gr) || !gen_factor(lift_s->m, gs)) return fail(ALCH_E_UNSUPPORTED, "alch_pt_linear_create: index not served");
+    u32 d_rel = 0, mask = 0;
+    std::vector<int32_t> tab;
+    if (!gen_tunnel_table(ge, gr, gs, d_rel, tab, mask)) return fail(ALCH_E_INVALID, "alch_pt_linear_create: the indices do not form an extension pair");
+    if (ys_zp->n_elems != (size_t)d_rel)
+        return fail(ALCH_E_INVALID, "alch_pt_linear_create: ys must hold d_rel = phi(r)/phi(gcd(r, s)) = " + std::to_string(d_rel) + " elements");
+    const u64 p = rp->q[0];
+    if (int rc = pt_check_q("alch_pt_linear_create", lift_s, p, d_rel)) return rc;
+    // x_dec = lInv_R(x_pow), and every E-coefficient goes back through l_E before it is embedded: on the axes of the primes that
+    // divide e the two cancel, on the others lInv acts on the RELATIVE index alone (differences y_i - y_(i - m') along that axis).  It
+    // is folded into the values once, sum_i y_i (M g)_i = sum_i (M^T y)_i g_i, so that the evaluation gathers Pow coefficients as they
+    // are: along each such axis y'_(i0 m' + r) = y_(i0 m' + r) - y_((i0 + 1) m' + r), the last block unchanged.
+    const size_t ns = lift_s->n;
+    std::vector<int64_t> y((size_t)d_rel * ns);
+    int rc = transfer(rp, ys_zp->dptr, 0, d_rel, y.data(), false);
+    if (rc != ALCH_OK) return rc;
+    BIND(lift_s);
+    {
+        u32 rel_dim[GEN_MAXFACT];
+        for (int l = 0; l < gr.nfact; ++l) {
+            int ee = 0;
+            for (int le = 0; le < ge.nfact; ++le) if (ge.fact[le].p == gr.fact[l].p) ee = ge.fact[le].e;
+            u32 pw = 1;
+            for (int k = ee; k < gr.fact[l].e; ++k) pw *= (u32)gr.fact[l].p;
+            rel_dim[l] = ee ? pw : gr.fact[l].dim;
+        }
+        size_t inner = d_rel;                                         // stride (in relative indices) of axis l: product of the later dims
+        for (int l = 0; l < gr.nfact; ++l) {
+            inner /= rel_dim[l];
+            if (mask & (1u << l)) continue;                           // prime divides e: nothing to fold
+            const u32 mp = gr.fact[l].mp, dim = rel_dim[l];
+            for (size_t i = 0; i < d_rel; ++i) {
+                const u32 a = (u32)((i / inner) % dim);
+                if (a + mp >= dim) continue;                          // the last block keeps its value
+                const int64_t* hi = &y[(i + (size_t)mp * inner) * ns];
+                int64_t* lo = &y[i * ns];
+                for (size_t k = 0; k < ns; ++k) { const int64_t v = lo[k] - hi[k]; lo[k] = v < 0 ? v + (int64_t)p : v; }
+            }
+        }
+    }
+    const int L = lift_s->L;
+    std::vector<int64_t> yl((size_t)d_rel * ns * L);
+    for (size_t w = 0; w < (size_t)d_rel * ns; ++w) {
+        const int64_t v = y[w] % (int64_t)p;
+        const int64_t z = v > (int64_t)((p - 1) >> 1) ? v - (int64_t)p : v;
+        for (int j = 0; j < L; ++j) {
+            const int64_t q = (int64_t)lift_s->q[j];
+            int64_t r = z % q;
+            yl[w * L + j] = r < 0 ? r + q : r;
+        }
+    }
+    alch_ptlin* f = new alch_ptlin();
+    f->lift = lift_s; f->m_r = m_r; f->n_r = gr.n; f->d_rel = d_rel; f->p = p;
+    if (hipMalloc(&f->ys, (size_t)d_rel * elem_bytes(lift_s)) != hipSuccess || hipMalloc((void**)&f->table, tab.size() * sizeof(int32_t)) != hipSuccess) {
+        alch_pt_linear_free(f);
+        return fail(ALCH_E_NOMEM, "hipMalloc(linear function) failed");
+    }
+    if (hipMemcpy(f->table, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { alch_pt_linear_free(f); return fail(ALCH_E_HIP, "linear-function table upload failed"); }
+    rc = transfer(lift_s, f->ys, 0, d_rel, yl.data(), true);
+    if (rc == ALCH_OK) rc = ALCH_BY_WORD(lift_s, do_crt, lift_s, f->ys, 0, d_rel, false);
+    if (rc == ALCH_OK) rc = ALCH_BY_WORD(lift_s, tunnel_to_mont, lift_s, f->ys, f->ys, d_rel);
+    if (rc != ALCH_OK) { alch_pt_linear_free(f); return rc; }
+    if (hipStreamSynchronize(lift_s->stream) != hipSuccess) { alch_pt_linear_free(f); return fail(ALCH_E_HIP, "linear-function setup failed"); }
+    *out = f;
+    return ALCH_OK;
+} catch (...) { return abi_catch(); }
+
+// dst[b] = sum_i y_i * embed(coeffsDec(src[b])_i): gather + lift, forward transforms, inner product, inverse transform, closing lift;
+// d_rel + 1 lifting-ring elements of scratch per batch element, chunked under scratch_mib.
+template <typename W>
+static int do_pt_eval_lin(const alch_ptlin* f, const alch_ring* rd, const void* src, void* dst, size_t count) {
+    alch_ring* lift = f->lift;
+    const size_t eb = elem_bytes(lift), D = f->d_rel;
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(count, (lift->scratch_mib << 20) / ((D + 1) * eb)));
+    if (int rc = ensure_ws(&lift->ws_lift, &lift->ws_lift_bytes, chunk * (D + 1) * eb)) return rc;
+    char* X = reinterpret_cast<char*>(lift->ws_lift);
+    for (size_t done = 0; done < count; done += chunk) {
+        const size_t now = std::min(chunk, count - done);
+        char* O = X + now * D * eb;
+        const u32* s = reinterpret_cast<const u32*>(src) + done * (size_t)f->n_r;
+        if (lift->n % 4 == 0)
+            hipLaunchKernelGGL((k_pt_lift_gather<W, 4>), dim3(ew_grid(now * D * lift->n / 4)), dim3(256), 0, lift->stream, dev_ring<W>(lift), (W*)X, s, f->table, now, (u32)D, f->n_r, (u32)f->p);
+        else
+            hipLaunchKernelGGL((k_pt_lift_gather<W, 1>), dim3(ew_grid(now * D * lift->n)), dim3(256), 0, lift->stream, dev_ring<W>(lift), (W*)X, s, f->table, now, (u32)D, f->n_r, (u32)f->p);
+        HIP_TRY(hipGetLastError());
+        if (int rc = do_crt<W>(lift, X, 0, now * D, false)) return rc;
+        const size_t words = now * elem_words(lift);
+        ALCH_LAUNCH_VW(k_pt_mac, lift, words, lift->stream, dev_ring<W>(lift), (W*)O, (const W*)X, (const W*)f->ys, now, (u32)D);
+        HIP_TRY(hipGetLastError());
+        if (int rc = do_crt<W>(lift, O, 0, now, true)) return rc;
+        if (int rc = launch_lift<W>(lift, rd, O, reinterpret_cast<char*>(dst) + done * (size_t)lift->n * 4, nullptr, now, 1)) return rc;
+    }
+    return ALCH_OK;
+}
+
+extern "C" int alch_pt_eval_lin(const void* handle, const alch_buf* src_zp, alch_buf* dst_zp, size_t count, unsigned flags) try {
+    const alch_ptlin* f = reinterpret_cast<const alch_ptlin*>(handle);
+    if (!f || !src_zp || !dst_zp) return fail(ALCH_E_INVALID, "alch_pt_eval_lin: null argument");
+    alch_ring* lift = f->lift;
+    BIND(lift);
+    alch_ring *rs = src_zp->ring, *rd = dst_zp->ring;
+    if (flags) return fail(ALCH_E_INVALID, "alch_pt_eval_lin: no flag is defined");
+    if (int rc = pt_check_zp("alch_pt_eval_lin", rs)) return rc;
+    if (int rc = pt_check_zp("alch_pt_eval_lin", rd)) return rc;
+    if (rs->q[0] != f->p || rd->q[0] != f->p) return fail(ALCH_E_INVALID, "alch_pt_eval_lin: source and destination carry the modulus of the linear function");
+    if (rs->m != f->m_r || rs->n != f->n_r) return fail(ALCH_E_INVALID, "alch_pt_eval_lin: the source ring must have the function's source index");
+    if (rs->device != lift->device) return fail(ALCH_E_INVALID, "alch_pt_eval_lin: the rings live on different devices");
+    if (int rc = pt_check_lift("alch_pt_eval_lin", lift, rd)) return rc;
+    if (!range_ok(0, count, src_zp->n_elems) || !range_ok(0, count, dst_zp->n_elems)) return fail(ALCH_E_INVALID, "alch_pt_eval_lin: count out of bounds");
+    if (count == 0) return ALCH_OK;
+    if (bytes_overlap(dst_zp->dptr, count * elem_bytes(rd), src_zp->dptr, count * elem_bytes(rs)))
+        return fail(ALCH_E_INVALID, "alch_pt_eval_lin: the destination overlaps the source");
+    int rc;
+    if ((rc = ext_order(lift, rs, true)) != ALCH_OK || (rc = ext_order(lift, rd, true)) != ALCH_OK) return rc;
+    if ((rc = ALCH_BY_WORD(lift, do_pt_eval_lin, f, rd, src_zp->dptr, dst_zp->dptr, count)) != ALCH_OK) return rc;
+    if ((rc = ext_order(lift, rs, false)) != ALCH_OK) return rc;
+    return ext_order(lift, rd, false);
+} catch (...) { return abi_catch(); }
+
+extern "C" int alch_pt_rescale(const alch_buf* src_zp, alch_buf* dst_zp, size_t count) try {
+    if (!src_zp || !dst_zp) return fail(ALCH_E_INVALID, "alch_pt_rescale: null buffer");
+    alch_ring *rs = src_zp->ring, *rd = dst_zp->ring;
+    BIND(rd);
+    if (int rc = pt_check_zp("alch_pt_rescale", rs)) return rc;
+    if (int rc = pt_check_zp("alch_pt_rescale", rd)) return rc;
+    if (rs->m != rd->m || rs->n != rd->n) return fail(ALCH_E_INVALID, "alch_pt_rescale: both rings must have one cyclotomic index");
+    if (rs->device != rd->device) return fail(ALCH_E_INVALID, "alch_pt_rescale: the rings live on different devices");
+    if (rs->q[0] % rd->q[0]) return fail(ALCH_E_INVALID, "alch_pt_rescale: the destination modulus must divide the source modulus");
+    if (!range_ok(0, count, src_zp->n_elems) || !range_ok(0, count, dst_zp->n_elems)) return fail(ALCH_E_INVALID, "alch_pt_rescale: count out of bounds");
+    if (count == 0) return ALCH_OK;
+    const size_t words = count * (size_t)rd->n;
+    if (src_zp->dptr != dst_zp->dptr && bytes_overlap(dst_zp->dptr, words * 4, src_zp->dptr, words * 4))
+        return fail(ALCH_E_INVALID, "alch_pt_rescale: overlapping ranges");
+    const u32 d = (u32)(rs->q[0] / rd->q[0]);
+    int rc;
+    if ((rc = ext_order(rd, rs, true)) != ALCH_OK) return rc;
+    HIP_TRY(hipMemsetAsync(rd->d_flag, 0, sizeof(int), rd->stream));
+    if (rd->n % 4 == 0)
+        hipLaunchKernelGGL((k_pt_rescale<4>), dim3(ew_grid(words / 4)), dim3(256), 0, rd->stream, (u32*)dst_zp->dptr, (const u32*)src_zp->dptr, words, d, rd->d_flag);
+    else
+        hipLaunchKernelGGL((k_pt_rescale<1>), dim3(ew_grid(words)), dim3(256), 0, rd->stream, (u32*)dst_zp->dptr, (const u32*)src_zp->dptr, words, d, rd->d_flag);
+    HIP_TRY(hipGetLastError());
+    if ((rc = ext_order(rd, rs, false)) != ALCH_OK) return rc;
+    int flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, rd->d_flag, sizeof(int), hipMemcpyDeviceToHost, rd->stream));
+    HIP_TRY(hipStreamSynchronize(rd->stream));
+    return flag ? ALCH_NOT_DIVISIBLE : ALCH_OK;
+} catch (...) { return abi_catch(); }
+
+template <typename W>
+static int do_add_bcast(alch_ring* r, void* dst, const void* src, const void* one, size_t count) {
+    const size_t words = count * elem_words(r);
+    ALCH_LAUNCH_VW(k_pt_add_bcast, r, words, r->stream, dev_ring<W>(r), (W*)dst, (const W*)src, (const W*)one, words);
+    HIP_TRY(hipGetLastError());
+    return ALCH_OK;
+}
+
+extern "C" int alch_buf_add_bcast(alch_buf* dst, const alch_buf* src, const alch_buf* one, size_t index, size_t count) try {
+    if (!dst || !src || !one) return fail(ALCH_E_INVALID, "alch_buf_add_bcast: null buffer");
+    alch_ring* r = dst->ring;
+    BIND(r);
+    if (src->ring != r || one->ring != r) return fail(ALCH_E_INVALID, "alch_buf_add_bcast: buffers belong to different rings");
+    if (r->zdom) return fail(ALCH_E_UNSUPPORTED, "alch_buf_add_bcast: not served on the integers");
+    if (index >= one->n_elems) return fail(ALCH_E_INVALID, "alch_buf_add_bcast: index out of bounds");
+    if (!range_ok(0, count, dst->n_elems) || !range_ok(0, count, src->n_elems)) return fail(ALCH_E_INVALID, "alch_buf_add_bcast: count out of bounds");
+    if (count == 0) return ALCH_OK;
+    const size_t eb = elem_bytes(r);
+    const char* o = reinterpret_cast<const char*>(one->dptr) + index * eb;
+    if (bytes_overlap(dst->dptr, count * eb, o, eb) || (dst->dptr != src->dptr && bytes_overlap(dst->dptr, count * eb, src->dptr, count * eb)))
+        return fail(ALCH_E_INVALID, "alch_buf_add_bcast: overlapping ranges");
+    return ALCH_BY_WORD(r, do_add_bcast, r, dst->dptr, src->dptr, o, count);
 } catch (...) { return abi_catch(); }
 
 #include "tensor_ext.inc.hpp"

@@ -573,6 +573,17 @@ struct PtCyc {
     std::vector<int64_t> v;          // phi(m) residues in [0, p)
 };
 
+// A batch of plaintext ring elements resident in HBM: `count` elements of Z_p[zeta_m] on the Pow basis in one alch_buf of the ring
+// without CRT basis.  Value semantics like PtCyc: the batch operations of PtOps return new batches (copies share the buffer).
+struct PtBatch {
+    uint32_t m = 1;
+    int64_t p = 2;
+    size_t count = 0;
+    const Ring* ring = nullptr;
+    std::shared_ptr<DevElem> d;
+    alch_buf* buf() const { return d->b; }
+};
+
 class PtOps {
 public:
     PtOps(RingCache& rc, std::vector<uint64_t> lift_primes) : rc_(rc), lp_(std::move(lift_primes)) {
@@ -638,9 +649,66 @@ public:
         return even;
     }
 
+    // ---- the same operations on resident batches (include/alchemy_hip.h, "plaintext ring elements on resident batches") ----
+    const Ring& zpRing(uint32_t m, int64_t p) const { return rc_.get(m, {(uint64_t)p}, false); }
+    const Ring& liftRing(uint32_t m) const { return rc_.get(m, lp_, true); }
+    PtBatch alloc(uint32_t m, int64_t p, size_t count) const {
+        const Ring& r = zpRing(m, p);
+        return PtBatch{m, p, count, &r, DevElem::make(r.handle(), count)};
+    }
+    PtBatch upload(const std::vector<PtCyc>& xs) const {
+        if (xs.empty()) throw std::runtime_error("PtOps::upload: empty batch");
+        PtBatch o = alloc(xs[0].m, xs[0].p, xs.size());
+        const size_t n = o.ring->n();
+        std::vector<int64_t> host(xs.size() * n);
+        for (size_t b = 0; b < xs.size(); ++b) {
+            if (xs[b].m != o.m || xs[b].p != o.p) throw std::runtime_error("PtOps::upload: mixed rings");
+            const PtCyc x = to(xs[b], Basis::Pow);
+            std::copy(x.v.begin(), x.v.end(), host.begin() + b * n);
+        }
+        check(alch_buf_upload(o.buf(), 0, o.count, host.data()), "alch_buf_upload (plaintext batch)");
+        return o;
+    }
+    std::vector<PtCyc> download(const PtBatch& a, size_t first, size_t count) const {
+        const size_t n = a.ring->n();
+        std::vector<int64_t> host(count * n);
+        check(alch_buf_download(a.buf(), first, count, host.data()), "alch_buf_download (plaintext batch)");
+        std::vector<PtCyc> out;
+        for (size_t b = 0; b < count; ++b)
+            out.push_back(PtCyc{a.m, a.p, Basis::Pow, std::vector<int64_t>(host.begin() + b * n, host.begin() + (b + 1) * n)});
+        return out;
+    }
+    std::vector<PtCyc> download(const PtBatch& a) const { return download(a, 0, a.count); }
+    PtBatch mul(const PtBatch& a, const PtBatch& b) const {
+        if (a.ring != b.ring || a.count != b.count) throw std::runtime_error("PtOps::mul: batches of different rings or sizes");
+        PtBatch o = alloc(a.m, a.p, a.count);
+        check(alch_pt_mul(liftRing(a.m).handle(), o.buf(), a.buf(), b.buf(), a.count, 0), "alch_pt_mul");
+        return o;
+    }
+    PtBatch addScalar(const PtBatch& a, int64_t s) const {
+        std::vector<int64_t> lit(a.ring->n(), 0);
+        lit[0] = ((s % a.p) + a.p) % a.p;
+        std::shared_ptr<DevElem>& one = lits_[std::make_tuple(a.m, a.p, lit[0])];          // one resident literal per (ring, scalar)
+        if (!one) {
+            one = DevElem::make(a.ring->handle(), 1);
+            check(alch_buf_upload(one->b, 0, 1, lit.data()), "alch_buf_upload (literal)");
+        }
+        PtBatch o = alloc(a.m, a.p, a.count);
+        check(alch_buf_add_bcast(o.buf(), a.buf(), one->b, 0, a.count), "alch_buf_add_bcast");
+        return o;
+    }
+    // div2_ on a batch: false when some coefficient of the batch was odd (the floor quotients are written, as in div2 above)
+    bool div2(const PtBatch& a, PtBatch& out) const {
+        out = alloc(a.m, a.p / 2, a.count);
+        const int rc = alch_pt_rescale(a.buf(), out.buf(), a.count);
+        check(rc, "alch_pt_rescale");
+        return rc != ALCH_NOT_DIVISIBLE;
+    }
+
 private:
     RingCache& rc_;
     std::vector<uint64_t> lp_;
+    mutable std::map<std::tuple<uint32_t, int64_t, int64_t>, std::shared_ptr<DevElem>> lits_;
 };
 
 // Cyc crtSet over Z_{p^e} (p = 2 here): Tensor crtSetDec of the p-free parts of (m, m') over F_p, lifted, taken to the Pow basis,
@@ -673,6 +741,7 @@ inline std::vector<PtCyc> crtSet(PtOps& ops, uint32_t m, uint32_t mbig, int64_t 
 struct Linear {
     uint32_t e = 1, r = 1, s = 1;
     std::vector<PtCyc> ys;           // over S, Pow basis
+    mutable std::shared_ptr<void> dev;   // the library's resident form (alch_pt_linear_create), made by the first batch evaluation
 };
 
 // decToCRT (examples/Common.hs:65-75): the relative decoding basis of R / E to the first dim = phi(r)/phi(e) elements of the
@@ -698,6 +767,20 @@ inline PtCyc evalLin(PtOps& ops, const Linear& f, const PtCyc& x) {
         acc = i ? ops.add(acc, term) : term;
     }
     return acc;
+}
+
+// evalLin on a resident batch: one alch_pt_eval_lin call; the function's handle is created on first use and kept by the Linear.
+inline PtBatch evalLin(PtOps& ops, const Linear& f, const PtBatch& x) {
+    if (x.m != f.r) throw std::runtime_error("evalLin: the batch is not over the function's source index");
+    if (!f.dev) {
+        const PtBatch ys = ops.upload(f.ys);
+        void* h = nullptr;
+        check(alch_pt_linear_create(ops.liftRing(f.s).handle(), ys.buf(), f.r, &h), "alch_pt_linear_create");
+        f.dev = std::shared_ptr<void>(h, [](void* p) { alch_pt_linear_free(p); });
+    }
+    PtBatch o = ops.alloc(f.s, x.p, x.count);
+    check(alch_pt_eval_lin(f.dev.get(), x.buf(), o.buf(), x.count, 0), "alch_pt_eval_lin");
+    return o;
 }
 
 }  // namespace gen

@@ -13,7 +13,9 @@
 // max |c(s)| / q -- what the ERW interpreter logs (Crypto/Alchemy/Interpreter/ErrorRateWriter.hs:70-75, Eval.hs:151-160) -- is printed.
 //
 //   homomrlwr_replay [batch] [--seed N] [--dump DIR] [--per-element] [--per-element-resident] [--per-element-zip-host]
-//                    [--host-mode buffers|resident] [--var-scale F] [--quiet-stages] [--device-decrypt]
+//                    [--host-mode buffers|resident] [--var-scale F] [--quiet-stages] [--device-decrypt] [--device-plaintext]
+// --device-plaintext computes the plaintext side (eval ringRound (s * a)) on resident batches -- PtBatch over alch_pt_mul, alch_pt_eval_lin,
+// alch_pt_rescale and alch_buf_add_bcast, one call per operation for all inputs -- instead of one ring element at a time; same lines, same PASS.
 // --device-decrypt runs the closing check (decrypt and error rate of every result) through decryptBatch -- one alch_ct_decrypt_lift
 // call on the resident batch, then divG / twace / l on the plaintext rings -- instead of one host-side decrypt per ciphertext; the
 // PASS line and the statistics are the same.
@@ -58,7 +60,7 @@ int main(int argc, char** argv) {
     size_t B = 4;
     uint64_t seed = 2026;
     std::string dump;
-    bool per_element = false, per_resident = false, per_ziphost = false, quiet = false, device_decrypt = false;
+    bool per_element = false, per_resident = false, per_ziphost = false, quiet = false, device_decrypt = false, device_plaintext = false;
     double var_scale = 1.0;
     Mode host_mode = Mode::Resident;
     for (int i = 1; i < argc; ++i) {
@@ -69,6 +71,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--per-element-zip-host")) per_ziphost = true;
         else if (!strcmp(argv[i], "--quiet-stages")) quiet = true;
         else if (!strcmp(argv[i], "--device-decrypt")) device_decrypt = true;
+        else if (!strcmp(argv[i], "--device-plaintext")) device_plaintext = true;
         else if (!strcmp(argv[i], "--var-scale") && i + 1 < argc) var_scale = atof(argv[++i]);
         else if (!strcmp(argv[i], "--host-mode") && i + 1 < argc) host_mode = !strcmp(argv[++i], "buffers") ? Mode::HostBuffers : Mode::Resident;
         else B = (size_t)atoi(argv[i]);
@@ -124,6 +127,22 @@ int main(int argc, char** argv) {
         std::vector<std::vector<PtCyc>> stage_pt(B);                 // after mulPublic, every hop, x(1+x) -- for the stage checks
         bool all_even = true;
         const int64_t zs[8] = {0, -2, -6, -12, -20, -30, -42, -56};    // z (1 - z), z = 1 .. 8   (Language/RescaleTree.hs:69)
+        if (device_plaintext) {
+            // the same evaluation on resident batches: one library call per operation for all B inputs (PtBatch, cycgen.hpp)
+            PtBatch x = ops.mul(ops.upload(std::vector<PtCyc>(B, s)), ops.upload(as));
+            stage_pt[0].push_back(ops.download(x, 0, 1)[0]);
+            for (int k = 0; k < 5; ++k) { x = evalLin(ops, lin[k], x); stage_pt[0].push_back(ops.download(x, 0, 1)[0]); }
+            PtBatch y = ops.mul(x, ops.addScalar(x, 1));
+            stage_pt[0].push_back(ops.download(y, 0, 1)[0]);
+            std::vector<PtBatch> t;
+            for (int j = 0; j < 8; ++j) { PtBatch h; all_even &= ops.div2(ops.addScalar(y, zs[j]), h); t.push_back(h); }
+            while (t.size() > 1) {
+                std::vector<PtBatch> nx;
+                for (size_t i = 0; i + 1 < t.size(); i += 2) { PtBatch h; all_even &= ops.div2(ops.mul(t[i], t[i + 1]), h); nx.push_back(h); }
+                t = nx;
+            }
+            expect = ops.download(t[0]);
+        } else
         for (size_t b = 0; b < B; ++b) {
             PtCyc x = ops.mul(s, as[b]);
             stage_pt[b].push_back(x);

@@ -508,6 +508,15 @@ mulFullGT :: Ptr AlchHint -> Ptr AlchBuf -> Ptr AlchBuf -> Ptr AlchBuf -> Int ->
 mulFullGT hint a b out batch spre =
   withArray spre $ \ps -> c_ctMulFull hint a b out (fromIntegral batch) ps 0 >>= check "alch_ct_mul_full"
 
+-- | Cyc @(*)@ on a device-resident batch of plaintext ring elements (E's @mul_@ on @Cyc t m zp@, reference Eval.hs:65-67): one
+-- 'c_ptMul' call over a lifting ring of the same index.  Arguments: lifting ring, destination, operands (Z_p buffers, Pow basis), count.
+ptMulGT :: Ptr AlchRing -> Ptr AlchBuf -> Ptr AlchBuf -> Ptr AlchBuf -> Int -> IO ()
+ptMulGT lift dst a b count = c_ptMul lift dst a b (fromIntegral count) 0 >>= check "alch_pt_mul"
+
+-- | @evalLin@ of a resident @Linear@ (reference Eval.hs:141) on a device-resident batch: one 'c_ptEvalLin' call.
+ptEvalLinGT :: Ptr () -> Ptr AlchBuf -> Ptr AlchBuf -> Int -> IO ()
+ptEvalLinGT f src dst count = c_ptEvalLin f src dst (fromIntegral count) 0 >>= check "alch_pt_eval_lin"
+
 -- | @c(s)@ of a device-resident batch on the decoding basis -- the object @errorTermUnrestricted@ lifts (reference Eval.hs:150-160):
 -- one 'c_ctErrorTerm' call.  Arguments: ciphertext buffer ((degree+1)*batch CRT-basis elements), batch, degree (1 or 2), the key as
 -- a one-element CRT-basis buffer, toLSD's per-limb scalar, output buffer (batch elements).

@@ -138,3 +138,12 @@ foreign import ccall safe   "alch_ct_mul_full"         c_ctMulFull       :: Ptr 
 foreign import ccall safe   "alch_ct_mul"              c_ctMul           :: Ptr AlchRing -> Ptr AlchBuf -> Ptr AlchBuf -> Ptr AlchBuf -> CSize -> Ptr Word64 -> CUInt -> IO CInt
 foreign import ccall safe   "alch_ct_key_switch_quad"  c_ctKeySwitchQuad :: Ptr AlchHint -> Ptr AlchBuf -> Ptr AlchBuf -> CSize -> Ptr Word64 -> CUInt -> IO CInt
 foreign import ccall safe   "alch_ct_mod_switch_deg"   c_ctModSwitchDeg  :: Ptr AlchBuf -> Ptr AlchBuf -> CSize -> CInt -> CUInt -> IO CInt
+-- plaintext ring elements on resident batches (added within library version 1.8): E's mul_, div2_, linearCyc_ and addLit_ on `Cyc t m zp`
+-- over a lifting ring; the linear-function handle is an opaque pointer
+foreign import ccall safe   "alch_pt_bound"            c_ptBound         :: Word32 -> Word64 -> Word32 -> Ptr Word64 -> Ptr Word64 -> IO CInt
+foreign import ccall safe   "alch_pt_mul"              c_ptMul           :: Ptr AlchRing -> Ptr AlchBuf -> Ptr AlchBuf -> Ptr AlchBuf -> CSize -> CUInt -> IO CInt
+foreign import ccall safe   "alch_pt_linear_create"    c_ptLinearCreate  :: Ptr AlchRing -> Ptr AlchBuf -> Word32 -> Ptr (Ptr ()) -> IO CInt
+foreign import ccall safe   "alch_pt_linear_free"      c_ptLinearFree    :: Ptr () -> IO CInt
+foreign import ccall safe   "alch_pt_eval_lin"         c_ptEvalLin       :: Ptr () -> Ptr AlchBuf -> Ptr AlchBuf -> CSize -> CUInt -> IO CInt
+foreign import ccall safe   "alch_pt_rescale"          c_ptRescale       :: Ptr AlchBuf -> Ptr AlchBuf -> CSize -> IO CInt
+foreign import ccall safe   "alch_buf_add_bcast"       c_bufAddBcast     :: Ptr AlchBuf -> Ptr AlchBuf -> Ptr AlchBuf -> CSize -> CSize -> IO CInt

@@ -83,7 +83,8 @@ typedef struct alch_tunnel alch_tunnel;
 const char *alch_last_error(void);
 /* Library/ABI version: (major<<16)|minor; the minor number goes up with every added capability (1.7: tunnels between two-power rings; 1.8: decrypt / error rates on resident batches).).
  * The step entry points of mul_ (alch_ct_mul, alch_ct_key_switch_quad, alch_ct_mod_switch_deg) were added WITHIN 1.8 -- the number did
- * not move; a host that wants them probes for the symbols (dlsym / ctypes hasattr). */
+ * not move; a host that wants them probes for the symbols (dlsym / ctypes hasattr).  So were the plaintext-side entry points
+ * (alch_pt_mul, alch_pt_linear_create / _free, alch_pt_eval_lin, alch_pt_rescale, alch_buf_add_bcast, alch_pt_bound). */
 uint32_t alch_version(void);
 
 /* ---- ring context ------------------------------------------------------------------------------
@@ -479,6 +480,57 @@ int alch_buf_lift(const alch_buf *src, size_t first, size_t count, alch_buf *dst
 int alch_ct_decrypt_lift(const alch_buf *in, size_t batch, int degree, const alch_buf *sk_crt, size_t sk_index,
                          const uint64_t *s_pre, alch_buf *dst_zp, size_t dst_first, uint64_t l_scalar, uint64_t *max_digits,
                          unsigned flags);
+
+/* ---- plaintext ring elements on resident batches (added within 1.8; probe for the symbols) ----------------------------------
+ * The reference runs every example twice, on plaintexts and homomorphically, and compares (examples/HomomRLWR.hs, examples/Arithmetic.hs):
+ * E evaluates the same mul_, div2_ and linearCyc_ on `Cyc t m zp` (Eval.hs:65-67, 72-88, 136-148) that PT2CT turns into ciphertext
+ * operations.  These entry points are that half on resident batches of rings WITHOUT a CRT basis (alch_ring_create_nocrt: Z_{2^e}, Z_7).
+ * Products run over a LIFTING RING, as Lol multiplies over an extension ring when Z_p has no CRT basis: any ring from alch_ring_create
+ * with the plaintext ring's index; Q = the product of its moduli.  Residues are lifted centred to the integers (|z| <= p/2), reduced
+ * into every limb, the ring operation runs exactly mod Q, and the result is lifted centred mod Q and reduced mod p.
+ * EXACTNESS.  On the powerful basis of index m the product of two elements with integer coefficients bounded by A has coefficients
+ * bounded by phi(m) * 2^w * A^2, w = the number of ODD primes of m: coefficient k of a*b is sum_{i,j} s(i,j,k) a_i b_j with s in
+ * {0, +1, -1}; the powerful basis is a tensor product over the prime powers m_l of m, and on each axis the exponent i_l + j_l mod m_l
+ * either is k_l itself or, past phi(m_l), reduces modulo Phi_{m_l} to minus a sum that contains k_l -- so for given (i, k) at most two
+ * j_l contribute, and for a power of two exactly one (the two candidates differ by m_l / 2 = phi(m_l)).  A sum of t such products:
+ *       bound(t, m, p) = t * phi(m) * 2^w * floor(p/2)^2          (alch_pt_bound computes it)
+ * Every entry point below that multiplies computes the bound and returns ALCH_E_INVALID, with a message, unless Q/2 > bound: a
+ * product that could wrap is never silently wrong.  (Two 31-bit primes, Q/2 ~ 2^61, hold phi(m) = 2^12, w = 3, t = 8 up to
+ * p = 2^22: far beyond the reference's Z_{2^e}, e <= 5.)
+ * RESTRICTIONS.  Every *_zp buffer belongs to a ring with exactly one modulus 2 <= p < 2^31 (32-bit words); the lifting ring has the
+ * SAME index as the plaintext ring it serves; alch_pt_rescale needs p' | p.  Powerful basis in and out everywhere.
+ * Common rules: count = 0 is ALCH_OK with nothing launched; ranges that would wrap are refused; inputs are never modified; work is
+ * queued on the lifting ring's stream (alch_pt_rescale: the destination ring's), and buffers of rings on other streams are ordered
+ * before and after it, as alch_ct_decrypt_lift orders its rings.  Products stay in the lifting ring's scratch, walked in chunks of at
+ * most "scratch_mib".  Statuses, in this order: ALCH_E_INVALID (null handle; buffers of different rings; unknown flag; a plaintext
+ * ring with several moduli or p >= 2^31; a lifting ring of another index), ALCH_E_NO_CRT (a lifting ring from
+ * alch_ring_create_nocrt), ALCH_E_INVALID (count out of bounds; Q too small for the bound; shifted overlaps), device errors last. */
+/* Host-only: the bound above for a t-term sum (1 <= terms <= 65536) as a 128-bit number (lo, hi). */
+int alch_pt_bound(uint32_t m, uint64_t p, uint32_t terms, uint64_t *lo, uint64_t *hi);
+/* Cyc (*) on plaintexts (Eval.hs:65-67 on `Cyc t m zp`): dst[e] = a[e] * b[e] in Z_p[zeta_m], e < count.  No mulG (that belongs to
+ * SymmSHE's product, not Cyc's).  One plaintext ring for the three buffers; dst may BE an operand.  flags: none defined (0). */
+int alch_pt_mul(alch_ring *lift, alch_buf *dst_zp, const alch_buf *a_zp, const alch_buf *b_zp, size_t count, unsigned flags);
+/* A `Linear t zp e r s` as linearDec builds it (examples/Common.hs:65-75), e = gcd(r, s): ys_zp holds EXACTLY d_rel = phi(r)/phi(e)
+ * elements of S_p (index s = lift_s's index) on the Pow basis, in the order of Tensor `coeffs` (ALCH_E_INVALID otherwise); they are
+ * kept resident, lifted, in the CRT basis of lift_s.  m_r = r.  Only lift_s needs a CRT basis; r and e may be any indices (two-power or
+ * not: only index tables touch them -- H0 = F128 -> H1 = F448 is served).  The handle is the library's `alch_ptlin`, declared here as
+ * an untyped `void *`: the mechanical check of the Haskell FFI module (tests/test_haskell_shim.py) maps every C parameter type of this
+ * header to an FFI type through a fixed table, and that table has no entry for a new handle type -- a typed `alch_ptlin *` would break it.
+ * Callers that want the type back wrap the pointer (alchemy_amd/host/cycgen.hpp: `Linear`; alchemy_amd.PtLinear).  Free it with
+ * alch_pt_linear_free when no call is using it.  The bound is taken with t = d_rel. */
+int alch_pt_linear_create(alch_ring *lift_s, const alch_buf *ys_zp, uint32_t m_r, void **out);
+int alch_pt_linear_free(void *f);
+/* evalLin (Eval.hs:141): dst[b] = sum_i y_i * embed(coeffsDec(src[b])_i), b < count.  src over index r, dst over index s, both on the
+ * Pow basis with the function's p: the l / lInv steps are inside the call (folded into the resident y_i, so the Z_p intermediates
+ * never exist in memory).  dst must not overlap src.  flags: none defined (0). */
+int alch_pt_eval_lin(const void *f, const alch_buf *src_zp, alch_buf *dst_zp, size_t count, unsigned flags);
+/* div2_ = rescalePow (Eval.hs:72-78) from Z_p to Z_p', p' | p, same index: dst = src / (p/p') coefficient-wise.  ALCH_NOT_DIVISIBLE
+ * when some coefficient of the range is not divisible; dst then holds the floor quotients.  The flag is reduced on the device: the
+ * call downloads one word and synchronises the destination ring's stream once. */
+int alch_pt_rescale(const alch_buf *src_zp, alch_buf *dst_zp, size_t count);
+/* addLit_ on a batch: dst[e] = src[e] + one[index], e < count; any ring with moduli (not the integers), any basis, one ring for the
+ * three buffers; dst may be src.  The x * (1 + x) of the rescale tree uses it. */
+int alch_buf_add_bcast(alch_buf *dst, const alch_buf *src, const alch_buf *one, size_t index, size_t count);
 
 /* ---- modSwitch building block (Eval.hs:130) ---------------------------------------
  * Rescale (a,b) -> b on Pow-basis elements: src lives in ring_src (L limbs), dst in ring_dst whose
