@@ -11,6 +11,13 @@
 // With 68 KiB LDS, 512 threads and <= 128 VGPRs per workgroup a CU holds two workgroups whose HBM phases
 // (tensor inputs, digits, hint, result stores) and barrier stalls hide under each other's butterflies;
 // the one-workgroup-per-CU form (k_ks_accum) idles the VALU during those phases.
+//
+// Arithmetic of the accumulators (31-bit moduli: 2q fits a word, 3q does not).  They are lazy in [0,2q) for the whole
+// item and are brought to [0,q) once, when they are stored.  The tensor part leaves its Montgomery reductions unreduced;
+// every digit is transformed NEGATED (the transform is linear, and negating is free where the digit is reduced:
+// q - z instead of z + q), so the hint step is  acc = sub_lazy(acc, mont_mul_lazy(x, h))  -- one subtraction with
+// borrow for two lazy values, 6 VALU instructions per product instead of the 8 of a sum of reduced values
+// (modarith.hpp).  Stage 0 of pass G is 8 instructions per coefficient pair for the same reason (xh - w1' yh).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -206,15 +213,15 @@ k_ks_accum_half(DevRing<u32> R, const u32* __restrict__ a, const u32* __restrict
     u32 po0 = 0, po1 = 0;                          // byte offsets of the previous item's two result rows
     bool pending = false;
     int prot = 0;
-    W pq = 0;                                      // modulus of the previous item (Q30: its accumulators are reduced at the store)
+    W pq = 0;                                      // modulus of the previous item (its accumulators, lazy in [0,2q), are reduced at the store)
     auto store_slice = [&](int r) {               // slice r of the previous item's results
         if (!pending) return;
         const u32 so = SLICE * (u32)((r + prot) & (EPT / 4 - 1));
         V v0, v1;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            v0[e] = Q30 ? csub(acc0[r * 4 + e], pq) : acc0[r * 4 + e];
-            v1[e] = Q30 ? csub(acc1[r * 4 + e], pq) : acc1[r * 4 + e];
+            v0[e] = csub(acc0[r * 4 + e], pq);
+            v1[e] = csub(acc1[r * 4 + e], pq);
         }
         buf_st16<ALCH_KS_NT_OUT>(ro, lane16, po0 + so, v0);
         buf_st16<ALCH_KS_NT_OUT>(ro, lane16, po1 + so, v1);
@@ -307,11 +314,14 @@ k_ks_accum_half(DevRing<u32> R, const u32* __restrict__ a, const u32* __restrict
                 const W x1 = csub(mont_mul_lazy(v[1][e], sr2, q, qni), q);          // a1 s R
                 const W c2 = csub(mont_mul_lazy(v[3][e], x1, q, qni), q);           // a1 b1 s
                 // sums of two products (< 2 q^2 < 2^32 q) share one Montgomery reduction
-                acc0[s * 4 + e] = csub(mont_red_lazy((u64)x0 * v[2][e] + (u64)c2 * v[4][e], q, qni), q);
+                // (!Q30: the accumulators stay lazy in [0,2q) until store_slice, so the reductions' results go in as they are)
+                const W r0 = mont_red_lazy((u64)x0 * v[2][e] + (u64)c2 * v[4][e], q, qni);
+                acc0[s * 4 + e] = Q30 ? csub(r0, q) : r0;
                 // three products (< 3 q^2 < 2^64): bring the high word below q first, then one reduction
                 const u64 p1 = (u64)x0 * v[3][e] + (u64)x1 * v[2][e] + (u64)c2 * v[5][e];
                 const u64 p1r = ((u64)csub((W)(p1 >> 32), q) << 32) | (u32)p1;        // high word < 1.5 q -> < q
-                acc1[s * 4 + e] = csub(mont_red_lazy(p1r, q, qni), q);
+                const W r1 = mont_red_lazy(p1r, q, qni);
+                acc1[s * 4 + e] = Q30 ? csub(r1, q) : r1;
             }
             if (s + ID < EPT / 4) issue(s + ID, in[s % ID]);  // refill the buffer just consumed
             __builtin_amdgcn_sched_barrier(0);   // at most two slices of loads live
@@ -334,12 +344,16 @@ k_ks_accum_half(DevRing<u32> R, const u32* __restrict__ a, const u32* __restrict
         // ---- global stages 0..2, HBM/L2 -> registers -> LDS
         if (!KS_DBG(256u)) {
             // stage 0 gives this half x + w1 y (lower) or x - w1 y (upper): the upper half multiplies by -w1 instead,
-            // so both run the same instructions (no select per coefficient)
+            // so both run the same instructions (no select per coefficient).
+            // !Q30: the NEGATED digit is transformed (the hint step subtracts its products, see sub_lazy): with
+            // xh = -x, yh = -y in [0,2q) stage 0 is  xh - w1' yh,  w1' = -w1 (lower half: -(x + w1 y)) or w1 (upper).
+            constexpr bool NEG = !Q30;                         // this instantiation transforms the negated digit
 #if ALCH_USE_PLANTARD
             const auto w1 = twf[1];
 #else
-            const W w1 = hf ? q - twf[1] : twf[1];
+            const W w1 = ((hf != 0) != NEG) ? q - twf[1] : twf[1];     // -w1 for the upper half, or for the lower half when negated
 #endif
+            const W nr1 = q - m.r1;                            // -1 in Montgomery form (unbalanced reduce of a negated digit)
             const auto w2 = twf[2 + hf], w3a = twf[4 + 2 * hf], w3b = twf[5 + 2 * hf];
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
@@ -357,7 +371,13 @@ k_ks_accum_half(DevRing<u32> R, const u32* __restrict__ a, const u32* __restrict
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         W xx, yr;
-                        if constexpr (BALANCED) {
+                        if constexpr (NEG && BALANCED) {                                            // the negated digit, both coefficients lazy
+                            xx = q - (W)zx[e];                                                      // |z| < q: (0, 2q)
+                            yr = q - (W)zy[e];
+                        } else if constexpr (NEG) {                                                 // (z + off) * -1: [0, 2q)
+                            xx = mont_mul_lazy((W)((W)zx[e] + R.dig_off[j]), nr1, q, qni);
+                            yr = mont_mul_lazy((W)((W)zy[e] + R.dig_off[j]), nr1, q, qni);
+                        } else if constexpr (BALANCED) {
                             // |z| < q: z mod q = min(z, z + q) as unsigned words (a negative z is a huge word)
                             const W zq = (W)zx[e] + q;
                             xx = zq < (W)zx[e] ? zq : (W)zx[e];
@@ -367,11 +387,13 @@ k_ks_accum_half(DevRing<u32> R, const u32* __restrict__ a, const u32* __restrict
                             yr = mont_mul_lazy((W)((W)zy[e] + R.dig_off[j]), m.r1, q, qni);
                         }
 #if ALCH_USE_PLANTARD
+                        if constexpr (NEG) xx = csub(xx, q);
                         const W t = tw_mul(yr, w1, q, qni);
                         u[k][e] = hf ? xx + (q - t) : xx + t;
 #else
-                        const W t = Q30 ? mont_mul_lazy(yr, w1, q, qni) : tw_mul(yr, w1, q, qni);     // Q30: [0,2q), the sum below 3q
-                        u[k][e] = xx + t;
+                        const W t = mont_mul_lazy(yr, w1, q, qni);                                      // [0, 2q)
+                        if constexpr (NEG) u[k][e] = sub_lazy(xx, t, 2u * q);                           // [0, 2q)
+                        else u[k][e] = xx + t;                                                          // Q30: below 3q
 #endif
                     }
                 }
@@ -459,9 +481,9 @@ k_ks_accum_half(DevRing<u32> R, const u32* __restrict__ a, const u32* __restrict
                 if constexpr (Q30) {                    // x in [0,4q), accumulators lazy in [0,2q)
                     acc0[r * 4 + e] = csub(acc0[r * 4 + e] + mont_mul_lazy(x[e], vh0[e], q, qni), 2u * q);
                     acc1[r * 4 + e] = csub(acc1[r * 4 + e] + mont_mul_lazy(x[e], vh1[e], q, qni), 2u * q);
-                } else {
-                acc0[r * 4 + e] = csub(acc0[r * 4 + e] + csub(mont_mul_lazy(x[e], vh0[e], q, qni), q), q);
-                acc1[r * 4 + e] = csub(acc1[r * 4 + e] + csub(mont_mul_lazy(x[e], vh1[e], q, qni), q), q);
+                } else {                                // x = transform of -d in [0,2q): acc - x h, one borrow-corrected subtraction
+                acc0[r * 4 + e] = sub_lazy(acc0[r * 4 + e], mont_mul_lazy(x[e], vh0[e], q, qni), 2u * q);
+                acc1[r * 4 + e] = sub_lazy(acc1[r * 4 + e], mont_mul_lazy(x[e], vh1[e], q, qni), 2u * q);
                 }
             }
             if (r + HD < EPT / 4) hint_issue(r + HD, ph0[r % HD], ph1[r % HD]);

@@ -9,7 +9,11 @@
 // Ranges.  mont_mul_lazy(a, b): a any word, b < q  ->  a*b*R^-1 mod q in [0, 2q).
 // Ring data are kept "lazy" in [0, 2q) between butterfly stages (2q < 2^32 / 2^63); csub() brings
 // a [0,2q) value to [0,q).  4q does not fit a 32-bit word for ALCHEMY's 31-bit moduli
-// (examples/HomomRLWR.hs:37-43), so Harvey's [0,4q) butterflies are not used.
+// (examples/HomomRLWR.hs:37-43), so Harvey's [0,4q) butterflies are not used; nor does 3q, so the SUM of a
+// lazy and a reduced value needs a conditional subtraction first.  The DIFFERENCE of two lazy values does fit:
+// sub_lazy(a, u, 2q): a, u in [0,2q)  ->  a - u mod q in [0,2q)  (a - u lies in (-2q, 2q); 2q is added back on a
+// borrow, so nothing wraps and neither operand is reduced first).  A lazy accumulator therefore takes a
+// product as  acc = sub_lazy(acc, mont_mul_lazy(-x, h))  in 6 instructions, against 8 for the sum of reduced values.
 #pragma once
 #include <stdint.h>
 
@@ -57,6 +61,8 @@ ALCH_HD u64 mont_mul_lazy(u64 a, u64 b, u64 q, u64 qni) {
 // [0,2q) -> [0,q).  x - q wraps to a huge value when x < q, so the unsigned min picks x.
 ALCH_HD u32 csub(u32 x, u32 q) { u32 y = x - q; return y < x ? y : x; }
 ALCH_HD u64 csub(u64 x, u64 q) { u64 y = x - q; return y < x ? y : x; }
+// a, u in [0,q2), q2 = 2q  ->  a - u (mod q) in [0,q2).  gfx950: v_sub_co_u32, v_cndmask_b32, v_add_u32.
+ALCH_HD u32 sub_lazy(u32 a, u32 u, u32 q2) { u32 d = a - u; return a < u ? d + q2 : d; }
 
 template <typename W>
 ALCH_HD W mont_mul(W a, W b, const ModP<W>& m) { return csub(mont_mul_lazy(a, b, m.q, m.qni), m.q); }
