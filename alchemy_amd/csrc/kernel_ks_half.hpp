@@ -17,7 +17,21 @@
 // every digit is transformed NEGATED (the transform is linear, and negating is free where the digit is reduced:
 // q - z instead of z + q), so the hint step is  acc = sub_lazy(acc, mont_mul_lazy(x, h))  -- one subtraction with
 // borrow for two lazy values, 6 VALU instructions per product instead of the 8 of a sum of reduced values
-// (modarith.hpp).  Stage 0 of pass G is 8 instructions per coefficient pair for the same reason (xh - w1' yh).
+// (modarith.hpp).
+//
+// Pass G, stages 0-1.  The `digits` argument holds centred lifts, |z| <= (q_i - 1)/2 < 2^30, so a digit times a centred constant
+// of limb j stays below 2^60 and four such products plus q_j 2^31 fit one Montgomery reduction.  Stages 0 and 1 of this half are
+// a linear map from the four coefficients k, k + n/4, k + n/2, k + 3n/4 to two outputs: stage01_signed (modarith.hpp) runs it as one
+// signed multiply-add chain per output pair, 5.5 VALU instructions per output where the lazy form (digit -> lazy word, stage 0 as
+// xh - w1' yh, one butterfly) took 13, and the same for every instantiation: BALANCED no longer matters (the products take any
+// digit of any modulus below 2^31, R.dig_off is not read), Q30 takes the [0,2q) outputs as [0,4q) values.  The negation of the
+// digit (!Q30) is in the sign of the four constants.  Stage 2 onwards is unchanged.
+// Who writes `digits`: only the tensor kernels launched just before this one -- k_tensor_intt (n = 2^11) and k_tensor_intt_split
+// (n = 2^15) for alch_ct_mul_relin, and the same two on the operands' ring for <UP> (alch_ct_mul_full), where digit i belongs to
+// limb i + dup of the hint's ring.  Both bring the coefficient to [0, q_i) and store  v > (q_i - 1)/2 ? v - q_i : v  (k_tensor_intt:
+// the `epi` lambda of its last inverse pass, kernels_ntt.hpp "W v = csub(x[k], q); SW z = v > half ? ..."; k_tensor_intt_split: the
+// "centred lift, digit stores" loop of kernel_tensor_split.hpp, z0 / z1 from c0, c1 < q);  every q_i of a 32-bit ring is below 2^31.  The composed key switch (ks_stage, with or without a ready c2) feeds k_hint_mac*, never this kernel.
+// ALCH_USE_PLANTARD builds keep the previous pass G (their shared twiddles are not Montgomery words); so does -DALCH_KS_SIGNED01=0.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -39,6 +53,12 @@
 #ifndef ALCH_A_PARTIALS
 #define ALCH_A_PARTIALS 0
 #endif
+// 1: stages 0-1 of pass G as one signed sum over the centred digits (stage01_signed, modarith.hpp); 0: the lazy stage 0 and two
+// butterflies it replaced.  Plantard builds keep the old form (their twiddles are not Montgomery words).
+#ifndef ALCH_KS_SIGNED01
+#define ALCH_KS_SIGNED01 1
+#endif
+#define KS_SIGNED01 (ALCH_KS_SIGNED01 && !ALCH_USE_PLANTARD)
 // Ablation switches (ALCH_EXP_FLAGS; wrong results, timing only) exist in -DALCH_ABLATE builds alone: in the product
 // kernel they cost real instructions (the compiler hoists e.g. the "skip the tensor part" zero-fill in front of the branch).
 #ifdef ALCH_ABLATE
@@ -108,11 +128,6 @@ namespace alch {
 // y * twiddle, fully reduced, for either twiddle representation
 __device__ __forceinline__ u32 tw_mul(u32 y, u64 br, u32 q, u32) { return plant_mul(y, br, q); }
 __device__ __forceinline__ u32 tw_mul(u32 y, u32 w, u32 q, u32 qni) { return csub(mont_mul_lazy(y, w, q, qni), q); }
-
-__device__ __forceinline__ u32 mont_red_lazy(u64 p, u32 q, u32 qni) {       // p < 2^32 * q  ->  [0, 2q)
-    u32 m = (u32)p * qni;
-    return (u32)((p + (u64)m * q) >> 32);
-}
 
 // Global memory goes through buffer instructions: one descriptor per array (wave-uniform, from the kernel arguments),
 // the per-lane part of every address is the single VGPR `lane16` = threadIdx.x * 16 bytes, everything else (work
@@ -329,6 +344,10 @@ k_ks_accum_half(DevRing<u32> R, const u32* __restrict__ a, const u32* __restrict
         }
     }
     KS_STAMP(0);                                  // tensor part (c0, c1, diagonal digit)
+#if KS_SIGNED01
+    // the table words behind pass G's constants (w1, w2 of this half), fetched once per item into scalar registers
+    W tw1 = __builtin_amdgcn_readfirstlane(R.twf[j][1]), tw2 = __builtin_amdgcn_readfirstlane(R.twf[j][2 + hf]);
+#endif
     for (int i = 0; i < Ls; ++i) {
         if (i == js || KS_DBG(512u)) continue;
         const u32 d = ((KS_DBG(2u) ? (u32)(ct & 7) : (u32)ct) * (u32)Ls + (u32)i) * ROW;   // byte offset of digit i
@@ -338,11 +357,22 @@ k_ks_accum_half(DevRing<u32> R, const u32* __restrict__ a, const u32* __restrict
         const W* twm = R.twf[j];                        // Montgomery words (per-lane last pass)
         int tid = threadIdx.x;
         asm volatile("" : "+s"(twf), "+s"(twm), "+v"(tid));
+#if KS_SIGNED01
+        asm volatile("" : "+s"(tw1), "+s"(tw2));
+        // Constants of stage01_signed for this item (limb j, half hf), centred; negated where the negated digit is transformed (!Q30).
+        // s = +1 (lower half) or -1: c0 = R, c2 = s w1, c1 = w2, c3 = s w1 w2, all in Montgomery form.  ~25 scalar instructions per
+        // digit from the two table words: nothing derived from them is live across the digit loop.
+        const W w1s = hf ? q - tw1 : tw1;
+        const int32_t sc0 = centre_const(m.r1, q, !Q30), sc1 = centre_const(tw2, q, !Q30), sc2 = centre_const(w1s, q, !Q30),
+                      sc3 = centre_const(mont_mul(w1s, tw2, m), q, !Q30);
+#endif
         KS_SYNC();      // previous transform's last pass has finished reading LDS
         KS_STAMP(1);                              // barrier before pass G
 
         // ---- global stages 0..2, HBM/L2 -> registers -> LDS
         if (!KS_DBG(256u)) {
+            const auto w3a = twf[4 + 2 * hf], w3b = twf[5 + 2 * hf];
+#if !KS_SIGNED01
             // stage 0 gives this half x + w1 y (lower) or x - w1 y (upper): the upper half multiplies by -w1 instead,
             // so both run the same instructions (no select per coefficient).
             // !Q30: the NEGATED digit is transformed (the hint step subtracts its products, see sub_lazy): with
@@ -354,7 +384,8 @@ k_ks_accum_half(DevRing<u32> R, const u32* __restrict__ a, const u32* __restrict
             const W w1 = ((hf != 0) != NEG) ? q - twf[1] : twf[1];     // -w1 for the upper half, or for the lower half when negated
 #endif
             const W nr1 = q - m.r1;                            // -1 in Montgomery form (unbalanced reduce of a negated digit)
-            const auto w2 = twf[2 + hf], w3a = twf[4 + 2 * hf], w3b = twf[5 + 2 * hf];
+            const auto w2 = twf[2 + hf];
+#endif
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
                 const int lo4 = (tid + T * g) * 4;                    // coefficients lo4..lo4+3 of each eighth
@@ -365,6 +396,19 @@ k_ks_accum_half(DevRing<u32> R, const u32* __restrict__ a, const u32* __restrict
                     zxs[k] = __builtin_bit_cast(SV, buf_ld16(rd, lane16, d + (u32)(k * (N / 8) + T * g * 4) * 4u));
                     zys[k] = __builtin_bit_cast(SV, buf_ld16(rd, lane16, d + (u32)((k + 4) * (N / 8) + T * g * 4) * 4u));
                 }
+#if KS_SIGNED01
+                // Stages 0-1 straight from the centred digits (|z| <= (q_i - 1)/2 < 2^30, see the header): each pair of outputs is one
+                // signed multiply-add chain with one reduction per output, lazy in [0,2q) -- what stage 2 takes (Q30: [0,4q)).
+#pragma unroll
+                for (int k = 0; k < 2; ++k)                           // eighths k, k + 2 of the lower half with k + 4, k + 6 of the upper
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        W y0, y2;
+                        stage01_signed(zxs[k][e], zxs[k + 2][e], zys[k][e], zys[k + 2][e], sc0, sc1, sc2, sc3, q, qni, y0, y2);
+                        u[k][e] = y0; u[k + 2][e] = y2;
+                    }
+#else
+                // the form stage01_signed replaced: digit -> lazy word, lazy stage 0, two butterflies of stage 1
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const SV zx = zxs[k], zy = zys[k];
@@ -403,13 +447,22 @@ k_ks_accum_half(DevRing<u32> R, const u32* __restrict__ a, const u32* __restrict
                     if constexpr (Q30) {
                         bfly_fwd4(u0, u2, w2, q, qni);
                         bfly_fwd4(u1, u3, w2, q, qni);
+                    } else {
+                        bfly_fwd(u0, u2, w2, q, qni);
+                        bfly_fwd(u1, u3, w2, q, qni);
+                    }
+                    u[0][e] = u0; u[1][e] = u1; u[2][e] = u2; u[3][e] = u3;
+                }
+#endif  // KS_SIGNED01
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {                         // stage 2
+                    W u0 = u[0][e], u1 = u[1][e], u2 = u[2][e], u3 = u[3][e];
+                    if constexpr (Q30) {
                         bfly_fwd4(u0, u1, w3a, q, qni);
                         bfly_fwd4(u2, u3, w3b, q, qni);
                     } else {
-                    bfly_fwd(u0, u2, w2, q, qni);
-                    bfly_fwd(u1, u3, w2, q, qni);
-                    bfly_fwd(u0, u1, w3a, q, qni);
-                    bfly_fwd(u2, u3, w3b, q, qni);
+                        bfly_fwd(u0, u1, w3a, q, qni);
+                        bfly_fwd(u2, u3, w3b, q, qni);
                     }
                     u[0][e] = u0; u[1][e] = u1; u[2][e] = u2; u[3][e] = u3;
                 }
