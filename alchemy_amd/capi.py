@@ -423,7 +423,8 @@ class Tunnel:
 
     def free(self):
         if getattr(self, "_h", None):
-            self.ring_s._l.alch_tunnel_free(self._h)
+            if getattr(self.ring_r, "_h", None) and getattr(self.ring_s, "_h", None):      # see Buf.free
+                self.ring_s._l.alch_tunnel_free(self._h)
             self._h = None
 
     def __del__(self):
@@ -444,7 +445,10 @@ class Buf:
 
     def free(self):
         if getattr(self, "_h", None):
-            self.ring._l.alch_buf_free(self._h)
+            # alch_buf_free returns the allocation to its ring's pool.  The finalizers of a garbage cycle (a failed test's frames,
+            # say) run in any order: once the ring has been destroyed the handle is dropped, not freed into freed memory.
+            if getattr(self.ring, "_h", None):
+                self.ring._l.alch_buf_free(self._h)
             self._h = None
 
     def __del__(self):
@@ -579,7 +583,8 @@ class Hint:
 
     def free(self):
         if getattr(self, "_h", None):
-            self.ring._l.alch_hint_free(self._h)
+            if getattr(self.ring, "_h", None):                  # see Buf.free
+                self.ring._l.alch_hint_free(self._h)
             self._h = None
 
     def __del__(self):

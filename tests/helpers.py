@@ -139,6 +139,55 @@ def primes_1_mod(m, count, lo=0):
     return out
 
 
+def primes_below(m, count, hi):
+    """The `count` largest primes q < hi with q = 1 (mod m), largest first: the mirror of primes_1_mod."""
+    from oracle.model import is_prime
+    out, q = [], ((hi - 2) // m) * m + 1
+    while len(out) < count:
+        assert q > 2, "fewer than `count` such primes"
+        if is_prime(q):
+            out.append(q)
+        q -= m
+    return out
+
+
+def worst_residues(q):
+    """0, 1, -2, -1 and the two residues next to q / 2: where a missing or doubled conditional subtraction shows."""
+    return [0, 1, q - 2, q - 1, (q - 1) // 2, (q + 1) // 2]
+
+
+def centred_extremes(q):
+    """Centred: 0, 1, -1, the largest positive value, the most negative one, the second largest."""
+    return [0, 1, q - 1, (q - 1) // 2, (q + 1) // 2, (q - 3) // 2]
+
+
+def extreme_words(rng, count, n, qs, extremes=worst_residues):
+    """(count, n, L) int64: per word one of the six residues extremes(q) (3 in 4) or a uniform one (1 in 4).  Every value is a
+    residue below q, so int64 holds it for any q < 2^63; nothing is added or multiplied in int64."""
+    limbs = []
+    for q in qs:
+        ext = np.array(extremes(q), dtype=np.int64)
+        assert ext.shape == (6,) and int(ext.min()) >= 0 and int(ext.max()) < q
+        pick = rng.integers(0, 8, size=(count, n))
+        fill = rng.integers(0, q, size=(count, n), dtype=np.int64)
+        limbs.append(np.where(pick < 6, ext[np.minimum(pick, 5)], fill))
+    return np.ascontiguousarray(np.stack(limbs, axis=2))
+
+
+def centred_extreme_words(rng, count, n, qs):
+    """extreme_words on the ends of the centred range (the digits of a TrivGad decomposition)."""
+    return extreme_words(rng, count, n, qs, extremes=centred_extremes)
+
+
+def assert_reduced(got, qs):
+    """Every stored word of a (..., L) result lies in [0, q_j)."""
+    got = np.asarray(got)
+    assert got.shape[-1] == len(qs)
+    assert int(got.min()) >= 0, "a stored word is negative as int64 (at or above 2^63)"
+    for j, q in enumerate(qs):
+        assert int(got[..., j].max()) < q, f"limb {j}: a stored word is not below its modulus"
+
+
 def oracle_full_mul_general(oracle_lib, m, qs_h, l_in, l_out, hint_crt, a0, a1, b0, b1, s_pre=None, pow_out=False):
     """PT2CT's whole mul_ on a GENERAL cyclotomic index, composed from the general C restatement's primitives:
     (*) with mulG on every product coefficient (Eval.hs:65-67), modSwitch up, keySwitchQuadCirc (Eval.hs:133),

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Randomised parity sweep of decrypt / error rates on resident batches: random ring (two-power 32 .. 2^14 or m = 2^a 3^b 5^c 7^d 13^e
-with phi(m) <= 3000), 1..8 moduli = 1 mod m (30-bit, or 59-bit on two-power rings, balanced or not), degree, batch and p.  Per case:
+with phi(m) <= 3000), 1..8 moduli = 1 mod m (30-bit, or 59-bit or just below 2^62 on two-power rings, balanced or not), words (uniform, or the extreme residues of
+helpers.extreme_words), degree, batch and p.  Per case:
 alch_ct_error_term against the C restatement (Horner on the CRT basis, crtInv, lInv) word for word, then alch_buf_lift of that result
 against Python integers (residues l * (x mod p) mod p and the digit vectors of max |x|), and alch_ct_decrypt_lift against both.
 usage: tests/sweeps/fuzz_parity_decrypt.py [seconds] [seed]"""
@@ -12,7 +13,7 @@ import alchemy_amd as A
 from alchemy_amd import capi
 from alchemy_amd import decrypt as D
 from oracle import cref
-from helpers import primes_1_mod
+from helpers import extreme_words, primes_1_mod, primes_below
 
 
 def phi(m):
@@ -64,7 +65,8 @@ def main():
         wide = pow2 and rng.random() < 0.3
         if wide:
             L = min(L, 4)
-            qs = primes_1_mod(m, L, lo=1 << 58)
+            top = rng.random() < 0.5                                    # the last primes below 2^62 instead of the first above 2^58
+            qs = primes_below(m, L, 1 << 62) if top else primes_1_mod(m, L, lo=1 << 58)
         elif rng.random() < 0.25 and L >= 2:                            # very different sizes: the unbalanced digit path
             qs = primes_1_mod(m, L - 1, lo=0) + primes_1_mod(m, 1, lo=1 << 29)
         else:
@@ -75,8 +77,10 @@ def main():
         p = rng.choice([2, 4, 7, 8, 32, 1 << 30, rng.randrange(2, 1 << 31)])
         l = rng.choice([1, p - 1, rng.randrange(p)])
         flags = capi.ALCH_POW_IN if rng.random() < 0.4 else 0
-        s_pre = None if rng.random() < 0.5 else [rng.randrange(1, q) for q in qs]
-        rnd = lambda c: np.stack([np.stack([nprng.integers(0, q, size=n, dtype=np.int64) for q in qs], axis=1) for _ in range(c)])
+        extreme = rng.random() < 0.3                                    # key, ciphertexts and scalar from the extreme residues
+        s_pre = None if rng.random() < 0.5 else [q - 1 for q in qs] if extreme else [rng.randrange(1, q) for q in qs]
+        if extreme: rnd = lambda c: extreme_words(nprng, c, n, qs)
+        else: rnd = lambda c: np.stack([np.stack([nprng.integers(0, q, size=n, dtype=np.int64) for q in qs], axis=1) for _ in range(c)])
         g, zp = A.Ring(m, qs), A.Ring(m, [p], nocrt=True)
         general = not (m >= 32 and m & (m - 1) == 0)
         o = cref.GenRing(m, qs) if general else cref.Ring(n, qs)
@@ -93,7 +97,7 @@ def main():
         gin = g.upload(np.stack([o.crtinv(np.ascontiguousarray(c)) for c in cts]) if flags else cts)
         gsk = g.upload(sk)
         et = D.error_term(gin, batch, gsk, degree=degree, s_pre=s_pre, flags=flags)
-        info = dict(m=m, qs=qs, degree=degree, batch=batch, p=p, l=l, flags=flags, seed=seed)
+        info = dict(m=m, qs=qs, degree=degree, batch=batch, p=p, l=l, flags=flags, extreme=extreme, seed=seed)
         if not np.array_equal(et.download(0, batch), want):
             print("MISMATCH error_term", info); return 1
         x = garner(want, qs)
@@ -108,7 +112,7 @@ def main():
             del dst
         del et, gin, gsk
         cases += 1
-        key = ("two-power" if pow2 else "general", "60-bit" if wide else "32-bit", f"L {L}")
+        key = ("two-power" if pow2 else "general", ("62-bit" if top else "60-bit") if wide else "32-bit", f"L {L}", "extreme" if extreme else "uniform")
         tally[key] = tally.get(key, 0) + 1
         if cases % 25 == 0: print(f"{cases} cases, {time.time() - t0:.0f} s", flush=True)
     for k in sorted(tally): print(k, tally[k])

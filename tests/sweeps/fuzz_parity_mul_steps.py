@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Randomised sweep of mul_ one SHE operation at a time against the fused entry points: random ring (two-power 32 .. 2^16, or
-m = 2^a 3^b 5^c 7^d 13^e with phi(m) <= 3000), 30-bit moduli or 59-bit on two-power rings, 2..5 limbs, TrivGad or BaseBGad 2, random
-launch options (split_fused, gen_fused, rs_lin, scratch_mib), batch 1..9, with and without s_pre.  Per case, on uniform words:
+m = 2^a 3^b 5^c 7^d 13^e with phi(m) <= 3000), 30-bit moduli, or 59-bit or just below 2^62 on two-power rings, 2..5 limbs, TrivGad or BaseBGad 2, random
+launch options (split_fused, gen_fused, rs_lin, scratch_mib), batch 1..9, with and without s_pre.  Per case, on uniform words or on the
+extreme residues of helpers.extreme_words (s_pre = -1 then):
   key_switch_quad(mul(a, b, s))                              == alch_ct_mul_relin(a, b, s)          (s also split between the calls)
   mod_switch(key_switch_quad(mod_switch_deg(mul, ., 2)))     == alch_ct_mul_full                    (TrivGad: up; BaseBGad 2: down)
   the same chain with ALCH_POW_IN / ALCH_POW_OUT on every step == the CRT-basis chain
@@ -15,7 +16,7 @@ import numpy as np
 import alchemy_amd as A
 from alchemy_amd import capi
 from alchemy_amd import mulsteps as MS
-from helpers import primes_1_mod
+from helpers import extreme_words, primes_1_mod, primes_below
 
 TRIV, BASE2, PIN, POUT = capi.ALCH_GAD_TRIV, capi.ALCH_GAD_BASE2, capi.ALCH_POW_IN, capi.ALCH_POW_OUT
 
@@ -32,6 +33,11 @@ def phi(m):
 
 def uniform(ring, count, seed):
     b = ring.alloc(count); b.fill_uniform(seed); return b
+
+
+def operands(ring, count, seed, extreme):
+    if not extreme: return uniform(ring, count, seed)
+    return ring.upload(extreme_words(np.random.default_rng(seed), count, ring.n, ring.qs))
 
 
 def same(x, y, count):
@@ -56,7 +62,9 @@ def main():
         wide = pow2 and m <= 1 << 16 and rng.random() < 0.3
         L = rng.randint(2, 4 if (wide or n >= 1 << 14) else 5)
         gadget = BASE2 if (n <= 4096 and rng.random() < 0.4) else TRIV
-        qs = primes_1_mod(m, L, lo=(1 << 58) if wide else rng.choice([1 << 28, 1 << 29]))
+        top = wide and rng.random() < 0.5                              # the top of the accepted range instead of its middle
+        qs = primes_below(m, L, 1 << 62) if top else primes_1_mod(m, L, lo=(1 << 58) if wide else rng.choice([1 << 28, 1 << 29]))
+        extreme = rng.random() < 0.3
         batch = rng.randint(1, 3 if n >= 1 << 14 else 9)
         rings = [A.Ring(m, qs[L - k:]) for k in range(1, L + 1)]
         opts = {}
@@ -64,12 +72,12 @@ def main():
         if rng.random() < 0.5: opts["gen_fused"] = rng.choice([0, 1])
         if rng.random() < 0.5: opts["rs_lin"] = rng.choice([0, 1])
         if rng.random() < 0.5: opts["scratch_mib"] = rng.choice([1, 2, 64])
-        info = dict(m=m, qs=qs, gadget=gadget, batch=batch, opts=opts, seed=seed)
+        info = dict(m=m, qs=qs, gadget=gadget, batch=batch, opts=opts, extreme=extreme, seed=seed)
         ring = rings[-1]
-        s = None if rng.random() < 0.3 else [rng.randrange(1, q) for q in qs]
-        a, b = uniform(ring, 2 * batch, rng.randrange(1 << 30)), uniform(ring, 2 * batch, rng.randrange(1 << 30))
+        s = None if rng.random() < 0.3 else [q - 1 for q in qs] if extreme else [rng.randrange(1, q) for q in qs]
+        a, b = operands(ring, 2 * batch, rng.randrange(1 << 30), extreme), operands(ring, 2 * batch, rng.randrange(1 << 30), extreme)
         sums = (a.checksum(), b.checksum())
-        hint = ring.hint_from_buf(uniform(ring, 2 * ring.gadget_digits(gadget), rng.randrange(1 << 30)), gadget=gadget)
+        hint = ring.hint_from_buf(operands(ring, 2 * ring.gadget_digits(gadget), rng.randrange(1 << 30), extreme), gadget=gadget)
         want = ring.alloc(2 * batch)
         ring.ct_mul_relin(hint, a, b, want, batch, s_pre=s)
         for r in rings:
@@ -98,8 +106,8 @@ def main():
                 l_in = rng.randint(3, L); l_h = rng.randint(2, l_in - 1); l_out = rng.randint(1, l_h - 1)
             r_in, r_h, r_out = rings[l_in - 1], rings[l_h - 1], rings[l_out - 1]
             info.update(limbs=(l_in, l_h, l_out))
-            fa, fb = uniform(r_in, 2 * batch, rng.randrange(1 << 30)), uniform(r_in, 2 * batch, rng.randrange(1 << 30))
-            fh = r_h.hint_from_buf(uniform(r_h, 2 * r_h.gadget_digits(gadget), rng.randrange(1 << 30)), gadget=gadget)
+            fa, fb = operands(r_in, 2 * batch, rng.randrange(1 << 30), extreme), operands(r_in, 2 * batch, rng.randrange(1 << 30), extreme)
+            fh = r_h.hint_from_buf(operands(r_h, 2 * r_h.gadget_digits(gadget), rng.randrange(1 << 30), extreme), gadget=gadget)
             fs = None if s is None else s[L - l_in:]
             pow_out = POUT if rng.random() < 0.3 else 0
             fwant, got = r_out.alloc(2 * batch), r_out.alloc(2 * batch)
@@ -115,7 +123,8 @@ def main():
         if (a.checksum(), b.checksum()) != sums:
             print("INPUT MODIFIED", info); return 1
         cases += 1
-        key = ("two-power" if pow2 else "general", "60-bit" if wide else "32-bit", "BaseBGad2" if gadget == BASE2 else "TrivGad")
+        key = ("two-power" if pow2 else "general", "62-bit" if top else "60-bit" if wide else "32-bit", "BaseBGad2" if gadget == BASE2 else "TrivGad",
+               "extreme" if extreme else "uniform")
         tally[key] = tally.get(key, 0) + 1
         if cases % 25 == 0: print(f"{cases} cases, {time.time() - t0:.0f} s", flush=True)
     for k in sorted(tally): print(k, tally[k])

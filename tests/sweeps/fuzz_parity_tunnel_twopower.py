@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Randomised parity sweep of alch_ct_tunnel between TWO-POWER rings of the radix-16 engine: random pairs of distinct (and, now and
-then, equal) indices 32 .. 2^13, 1..8 moduli = 1 mod the larger index near 2^28, 2^30 or 2^59 (32- and 64-bit words), TrivGad or
-BaseBGad 2 hints, ciphertexts 0..2 limbs below the hint's ring, random linear functions, hints, ciphertexts, encoding scalars, all four
+then, equal) indices 32 .. 2^13, 1..8 moduli = 1 mod the larger index near 2^28, 2^30, 2^59 or just below 2^62 (32- and 64-bit words), TrivGad or
+BaseBGad 2 hints, ciphertexts 0..2 limbs below the hint's ring, random linear functions, hints, ciphertexts, encoding scalars (uniform words, or the
+extreme residues of helpers.extreme_words with s_pre = -1), all four
 ALCH_POW_IN / ALCH_POW_OUT combinations, batches of 1..9 and a small scratch now and then (several chunks), against the C restatement's
 composition (tests/helpers.py::oracle_tunnel).  usage: tests/sweeps/fuzz_parity_tunnel_twopower.py [seconds] [seed] [max cases]"""
 import os, random, sys, time
@@ -11,7 +12,7 @@ import numpy as np
 import alchemy_amd as A
 from alchemy_amd import capi
 from oracle import cref
-from helpers import oracle_tunnel, primes_1_mod
+from helpers import extreme_words, oracle_tunnel, primes_1_mod, primes_below
 
 
 def main():
@@ -25,9 +26,9 @@ def main():
     while time.time() - t0 < budget and cases < max_cases:
         rp, sp = 1 << rng.randint(5, 13), 1 << rng.randint(5, 13)
         if rp == sp and rng.random() < 0.9: continue
-        lo = rng.choice([1 << 28, 1 << 30, 1 << 30, 1 << 59])
+        lo = rng.choice([1 << 28, 1 << 30, 1 << 30, 1 << 59, 1 << 62])
         L = rng.randint(1, 8)
-        qs = primes_1_mod(max(rp, sp), L, lo=lo)
+        qs = primes_below(max(rp, sp), L, 1 << 62) if lo == 1 << 62 else primes_1_mod(max(rp, sp), L, lo=lo)   # 2^62: the last primes BELOW it
         if lo < 1 << 31 and max(qs) >= 1 << 31: continue
         dup = rng.choice([0, 0, 1, 2])
         if dup >= L: dup = 0
@@ -38,9 +39,11 @@ def main():
         D = gs.gadget_digits(capi.ALCH_GAD_BASE2) if gadget == "base2" else L
         if d_rel * D * L * gs.n > 3_000_000: continue               # keep the oracle's work per case small
         batch = rng.randint(1, 9) if d_rel * D * gs.n < 300_000 else rng.randint(1, 2)
-        rnd = lambda c, n, ms: np.stack([np.stack([nprng.integers(0, q, size=n, dtype=np.int64) for q in ms], axis=1) for _ in range(c)])
+        extreme = rng.random() < 0.3
+        if extreme: rnd = lambda c, n, ms: extreme_words(nprng, c, n, ms)
+        else: rnd = lambda c, n, ms: np.stack([np.stack([nprng.integers(0, q, size=n, dtype=np.int64) for q in ms], axis=1) for _ in range(c)])
         lin, ks, cts = rnd(d_rel, gs.n, qs), rnd(2 * d_rel * D, gs.n, qs), rnd(2 * batch, gr.n, qs[dup:])
-        s_pre = None if rng.random() < 0.5 else [rng.randrange(1, q) for q in qs]
+        s_pre = None if rng.random() < 0.5 else [q - 1 for q in qs] if extreme else [rng.randrange(1, q) for q in qs]
         flags = rng.choice([0, 0, capi.ALCH_POW_IN, capi.ALCH_POW_OUT, capi.ALCH_POW_IN | capi.ALCH_POW_OUT])
         small_scratch = rng.random() < 0.25
         if small_scratch: gs.set_option("scratch_mib", 1)
@@ -57,7 +60,7 @@ def main():
         gin, out = gin_ring.upload(src), gs.alloc(2 * batch)
         tun.apply(gin, out, batch, s_pre=s_pre, flags=flags)
         got = out.download()
-        case = dict(rp=rp, sp=sp, qs=qs, dup=dup, gadget=gadget, batch=batch, flags=flags, small_scratch=small_scratch, seed=seed)
+        case = dict(rp=rp, sp=sp, qs=qs, dup=dup, gadget=gadget, batch=batch, flags=flags, small_scratch=small_scratch, extreme=extreme, seed=seed)
         for ct in range(batch):
             w0, w1 = oracle_tunnel(cref, rp, sp, qs, list(lin), list(ks), up[2 * ct], up[2 * ct + 1], s_pre,
                                    pow_out=bool(flags & capi.ALCH_POW_OUT), gadget=gadget)
@@ -66,7 +69,8 @@ def main():
         if not np.array_equal(gin.download(), src):
             print("INPUT MODIFIED", case); return 1
         cases += 1
-        key = (gadget, "up" if sp > rp else "down" if rp > sp else "same", "%d-bit" % (64 if lo > 1 << 31 else 32), "dup %d" % dup)
+        key = (gadget, "up" if sp > rp else "down" if rp > sp else "same", "62-bit" if lo == 1 << 62 else "%d-bit" % (64 if lo > 1 << 31 else 32), "dup %d" % dup,
+               "extreme" if extreme else "uniform")
         tally[key] = tally.get(key, 0) + 1
         if cases % 20 == 0: print(f"{cases} cases, {time.time() - t0:.0f} s", flush=True)
     for k in sorted(tally): print(k, tally[k])

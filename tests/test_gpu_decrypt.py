@@ -15,11 +15,13 @@ import pytest
 import alchemy_amd as A
 from alchemy_amd import capi
 from alchemy_amd import decrypt as D
-from helpers import primes_1_mod, to_aos
+from helpers import assert_reduced, extreme_words, primes_1_mod, primes_below, to_aos
+from test_gpu_word64_edges import EDGE_BAL, EDGE_UNBAL
 
 pytestmark = pytest.mark.gpu
 
 P_SET = [2, 8, 7, 1 << 30]
+P_MAX = (1 << 31) - 1                            # the largest destination modulus alch_buf_lift accepts; run by the 62-bit rows
 
 
 def to_digits(x, qs):
@@ -90,14 +92,25 @@ def lift_ring_cases():
     cases.append((512, 2, 30, True))            # n = 256: the smallest on the workgroup-per-element path
     cases.append((32, 4, 30, False))            # moduli of very different sizes: digits enter a limb through a full product
     cases.append((1 << 12, 3, 59, False))
+    for m, L in ((1 << 12, 3), (32, 4)):        # moduli just below 2^62, the top of the accepted range: k_lift<u64> with bal 1 and 0
+        cases.append((m, L, 62, True))
+        cases.append((m, L, 62, False))
+    cases.append((64, 2, 62, "edge_bal"))       # either side of the boundary q_i < 2 q_j that sets LiftPar::bal
+    cases.append((64, 2, 62, "edge_unbal"))
     return cases
 
 
 def moduli(m, L, bits, balanced):
+    """bits < 62: the first primes above 2^(bits-1); bits = 62: the last ones BELOW 2^62 (nothing at or above it is accepted)."""
+    if balanced in ("edge_bal", "edge_unbal"):
+        qs = EDGE_BAL if balanced == "edge_bal" else EDGE_UNBAL
+        assert all(2 * a > b for a in qs for b in qs) == (balanced == "edge_bal")
+        return qs
+    big = (lambda count: primes_below(m, count, 1 << 62)) if bits == 62 else (lambda count: primes_1_mod(m, count, 1 << (bits - 1)))
     if balanced:
-        return primes_1_mod(m, L, 1 << (bits - 1))
+        return big(L)
     lo = primes_1_mod(m, L - 1, 0)                                     # the smallest primes that are 1 mod m
-    return [lo[0], primes_1_mod(m, 1, 1 << (bits - 1))[0]] + lo[1:]
+    return [lo[0], big(1)[0]] + lo[1:]
 
 
 @pytest.mark.parametrize("m,L,bits,balanced", lift_ring_cases())
@@ -117,7 +130,7 @@ def test_lift_crafted(m, L, bits, balanced):
     want_digits = [to_digits(max(abs(v) for v in x), qs) for x in lifted]
     assert all(d == to_digits((cr.Q - 1) // 2, qs) for d in want_digits)
     lifted_np = np.array(lifted, dtype=object)
-    for p in P_SET:
+    for p in P_SET + ([P_MAX] if bits == 62 else []):
         zp = A.Ring(m, [p], nocrt=True)
         dst = zp.alloc(total + 3)
         for l in (1, p - 1):
@@ -127,6 +140,7 @@ def test_lift_crafted(m, L, bits, balanced):
                 before = dst.download()
                 digits = D.lift(src, dst, l=l, want_max=True, first=1, count=count, dst_first=2)
                 got = dst.download()
+                assert_reduced(got[2:2 + count], [p])
                 assert np.array_equal(got[2:2 + count, :, 0], want[:count]), (m, L, p, l, count)
                 assert np.array_equal(got[:2], before[:2]) and np.array_equal(got[2 + count:], before[2 + count:]), (m, L, p, l, count)
                 assert digits == want_digits[:count], (m, L, p, l, count)
@@ -146,7 +160,8 @@ def test_lift_crafted(m, L, bits, balanced):
 
 
 @pytest.mark.parametrize("m,L,bits,balanced", [(32, 3, 30, True), (420, 2, 30, True), (1 << 13, 3, 30, True), (1 << 13, 8, 30, True),
-                                               (1 << 12, 3, 59, True), (32, 4, 30, False), (512, 2, 30, True)])
+                                               (1 << 12, 3, 59, True), (32, 4, 30, False), (512, 2, 30, True),
+                                               (1 << 12, 3, 62, True), (32, 4, 62, False), (64, 2, 62, "edge_bal"), (64, 2, 62, "edge_unbal")])
 def test_lift_maximum_position_and_sign(m, L, bits, balanced):
     """The lexicographic maximum of |x|: small random elements with ONE planted magnitude M = Q // 3 + 5 at index 0, at n - 1, at
     n - 3 (a lane of the last wave), as -M, as +M and -M together, as +M against -(M + 1) (the negative wins by one: complement and
@@ -193,24 +208,30 @@ def oracle_error_term(O, general, comps, sk, s_pre):
     return O.linv(acc) if general else acc
 
 
-ERROR_TERM_RINGS = [(32, 2, 30, 3), (64, 3, 30, 3), (45, 3, 30, 3), (420, 2, 30, 3), (11648, 5, 30, 2), (1 << 12, 2, 60, 3), (1 << 17, 2, 30, 2)]
+ERROR_TERM_RINGS = [(32, 2, 30, 3), (64, 3, 30, 3), (45, 3, 30, 3), (420, 2, 30, 3), (11648, 5, 30, 2), (1 << 12, 2, 60, 3), (1 << 17, 2, 30, 2),
+                    (1 << 12, 2, 62, 3), (420, 2, 62, 3)]               # 62: just below 2^62, on extreme words
 
 
 @pytest.mark.parametrize("m,L,bits,batch", ERROR_TERM_RINGS)
 def test_error_term_matches_the_oracle(oracle_lib, m, L, bits, batch):
     """alch_ct_error_term on random ciphertext words (parity does not need them valid): degree 1 and 2, with and without s_pre, CRT
-    input and ALCH_POW_IN, written at an element offset of the output; equal to lInv(crtInv(Horner)) limb by limb; input untouched."""
-    qs = primes_1_mod(m, L, 1 << (bits - 1))
+    input and ALCH_POW_IN, written at an element offset of the output; equal to lInv(crtInv(Horner)) limb by limb; input untouched.
+    The 62-bit rows draw key, ciphertexts and scalar from the extreme residues (helpers.extreme_words, s_pre = -1)."""
+    qs = moduli(m, L, bits, True)
     ring = A.Ring(m, qs)
+    assert ring.word_bytes == (4 if bits <= 31 else 8)
     O, general = oracle_ring(oracle_lib, m, qs)
     rng = np.random.default_rng(m + L)
-    sk = rand_elems(rng, 2, ring.n, qs)
+    words = extreme_words if bits == 62 else rand_elems
+    sk = words(rng, 2, ring.n, qs)
     gsk = ring.upload(sk)
     for degree in (1, 2):
         per = degree + 1
-        cts = rand_elems(rng, per * batch, ring.n, qs)
+        cts = words(rng, per * batch, ring.n, qs)
         for with_s_pre in (False, True):
             s_pre = [int(rng.integers(1, q)) for q in qs] if with_s_pre else None
+            if with_s_pre and bits == 62:
+                s_pre = [q - 1 for q in qs]
             want = [oracle_error_term(O, general, [cts[per * b + c] for c in range(per)], sk[1], s_pre) for b in range(batch)]
             for flags in (0, capi.ALCH_POW_IN):
                 src = np.stack([O.crtinv(np.ascontiguousarray(c)) for c in cts]) if flags else cts
@@ -220,11 +241,44 @@ def test_error_term_matches_the_oracle(oracle_lib, m, L, bits, batch):
                 before = out.download()
                 D.error_term(gin, batch, gsk, degree=degree, s_pre=s_pre, flags=flags, out=out, out_first=1, sk_index=1)
                 got = out.download()
+                assert_reduced(got, qs)
                 for b in range(batch):
                     assert np.array_equal(got[1 + b], want[b]), (m, L, degree, with_s_pre, flags, b)
                 assert np.array_equal(got[0], before[0]) and np.array_equal(got[-1], before[-1])
                 assert np.array_equal(gin.download(), src)
                 del out, gin
+
+
+@pytest.mark.parametrize("m,L,balanced", [(1 << 12, 3, True), (32, 4, False), (64, 2, "edge_bal"), (64, 2, "edge_unbal")])
+def test_decrypt_lift_moduli_below_2_62(oracle_lib, m, L, balanced):
+    """alch_ct_decrypt_lift (k_ct_eval_sk<u64>, then k_lift<u64> with bal 1 and 0) on extreme words, s_pre = -1, at the top of the
+    accepted modulus range: residues modulo 2^31 - 1 (the largest destination modulus) and modulo 8 and the digit vectors of max |x|
+    against the oracle's c(s) lifted in Python integers."""
+    qs = moduli(m, L, 62, balanced)
+    ring = A.Ring(m, qs)
+    assert ring.word_bytes == 8
+    O, general = oracle_ring(oracle_lib, m, qs)
+    n, batch, Q = ring.n, 3, prod(qs)
+    rng = np.random.default_rng(62 + m + L)
+    sk, cts = extreme_words(rng, 1, n, qs), extreme_words(rng, 2 * batch, n, qs)
+    s_pre = [q - 1 for q in qs]
+    coef = [Q // q * pow(Q // q, -1, q) for q in qs]
+    lifted = []
+    for b in range(batch):
+        et = oracle_error_term(O, general, [cts[2 * b], cts[2 * b + 1]], sk[0], s_pre)
+        lifted.append([centred(sum(int(r) * c for r, c in zip(row, coef)), Q) for row in et])
+    gin, gsk = ring.upload(cts), ring.upload(sk)
+    for p in (P_MAX, 8):
+        zp = A.Ring(m, [p], nocrt=True)
+        dst = zp.alloc(batch)
+        digits = D.decrypt_lift(gin, batch, gsk, s_pre=s_pre, dst=dst, l=p - 1, want_max=True)
+        got = dst.download()
+        assert_reduced(got, [p])
+        for b in range(batch):
+            assert got[b, :, 0].tolist() == [v * (p - 1) % p for v in lifted[b]], (p, b)
+            assert digits[b] == to_digits(max(abs(v) for v in lifted[b]), qs), (p, b)
+        del dst
+    assert np.array_equal(gin.download(), cts)
 
 
 # ---- semantic cases ----------------------------------------------------------------------------------------------------------------

@@ -8,28 +8,11 @@ import numpy as np
 import pytest
 
 from conftest import CFG3_QS
-from helpers import oracle_full_mul
+from helpers import assert_reduced as _assert_reduced, extreme_words as _worst, oracle_full_mul
 from test_gpu_full_mul import SIX_QS
 from test_gpu_parity import EIGHT_QS, UNBAL_QS
 
 pytestmark = pytest.mark.gpu
-
-
-def _worst(rng, count, n, qs):
-    """(count, n, L) int64: per word one of the six extreme residues (3 in 4) or a uniform one (1 in 4)."""
-    limbs = []
-    for q in qs:
-        ext = np.array([0, 1, q - 2, q - 1, (q - 1) // 2, (q + 1) // 2], dtype=np.int64)
-        pick = rng.integers(0, 8, size=(count, n))
-        fill = rng.integers(0, q, size=(count, n), dtype=np.int64)
-        limbs.append(np.where(pick < 6, ext[np.minimum(pick, 5)], fill))
-    return np.ascontiguousarray(np.stack(limbs, axis=2))
-
-
-def _assert_reduced(got, qs):
-    assert int(got.min()) >= 0
-    for j, q in enumerate(qs):
-        assert int(got[..., j].max()) < q, f"limb {j}: a stored word is not below its modulus"
 
 
 def _relin_case(oracle_lib, n, qs, batch, seed, s_pre=None, diagonal_hint=False):

@@ -10,7 +10,7 @@ import pytest
 
 import alchemy_amd as A
 from alchemy_amd import capi
-from helpers import load_golden, oracle_tunnel, primes_1_mod, to_aos
+from helpers import assert_reduced, load_golden, oracle_tunnel, primes_1_mod, to_aos
 
 pytestmark = pytest.mark.gpu
 
@@ -44,20 +44,26 @@ def need_twopower_tunnels():
         pytest.fail(_SERVED[0])
 
 
-def check_parity(oracle_lib, rp, sp, qs, gadget, batch, with_s_pre, flag_sets=(0,), scratch_mib=None, seed=0):
+def check_parity(oracle_lib, rp, sp, qs, gadget, batch, with_s_pre, flag_sets=(0,), scratch_mib=None, seed=0, words=rand_elems,
+                 s_pre=None, word_bytes=None):
     """Random linear function, hints and ciphertexts (parity does not need them valid) through Tunnel.apply, every ciphertext
-    word for word against oracle_tunnel; the input buffer is left untouched."""
+    word for word against oracle_tunnel; every stored word below its modulus; the input buffer is left untouched.
+    words(rng, count, n, qs): the word generator (uniform unless given); s_pre: a scalar vector to use instead of a random one;
+    word_bytes: the word size both rings must have."""
     L = len(qs)
     gr, gs = A.Ring(rp, qs), A.Ring(sp, qs)
+    if word_bytes is not None:
+        assert gr.word_bytes == gs.word_bytes == word_bytes
     if scratch_mib is not None:
         gs.set_option("scratch_mib", scratch_mib)
     ep, d_rel = A.Tunnel.info(gr, gs)
     assert ep == min(rp, sp) and d_rel == max(1, rp // sp)
     D = gs.gadget_digits(GADGETS[gadget])
     rng = np.random.default_rng(rp * 131 + sp + 7 * L + seed)
-    lin, ks = rand_elems(rng, d_rel, gs.n, qs), rand_elems(rng, 2 * d_rel * D, gs.n, qs)
-    cts = rand_elems(rng, 2 * batch, gr.n, qs)
-    s_pre = [int(rng.integers(1, q)) for q in qs] if with_s_pre else None
+    lin, ks = words(rng, d_rel, gs.n, qs), words(rng, 2 * d_rel * D, gs.n, qs)
+    cts = words(rng, 2 * batch, gr.n, qs)
+    if s_pre is None:
+        s_pre = [int(rng.integers(1, q)) for q in qs] if with_s_pre else None
     want = [oracle_tunnel(oracle_lib, rp, sp, qs, list(lin), list(ks), cts[2 * ct], cts[2 * ct + 1], s_pre, gadget=gadget)
             for ct in range(batch)]
     Or, Os = oracle_lib.GenRing(rp, qs), oracle_lib.GenRing(sp, qs)
@@ -69,6 +75,7 @@ def check_parity(oracle_lib, rp, sp, qs, gadget, batch, with_s_pre, flag_sets=(0
         gout.fill_uniform(99)
         tun.apply(gin, gout, batch, s_pre=s_pre, flags=flags)
         got = gout.download()
+        assert_reduced(got, qs)
         for ct in range(batch):
             for comp in range(2):
                 w = want[ct][comp]
