@@ -40,6 +40,7 @@ SYMBOLS = [
     "alch_ct_mul", "alch_ct_key_switch_quad", "alch_ct_mod_switch_deg",
     "alch_pt_bound", "alch_pt_mul", "alch_pt_linear_create", "alch_pt_linear_free", "alch_pt_eval_lin", "alch_pt_rescale",
     "alch_buf_add_bcast",
+    "alch_ct_add",
 ]
 
 
@@ -173,6 +174,7 @@ def load_library():
         "alch_pt_eval_lin": [VP, VP, VP, C.c_size_t, C.c_uint],
         "alch_pt_rescale": [VP, VP, C.c_size_t],
         "alch_buf_add_bcast": [VP, VP, VP, C.c_size_t, C.c_size_t],
+        "alch_ct_add": [VP, C.c_size_t, VP, C.c_int, PU64, C.c_uint, VP, C.c_int, PU64, C.c_uint, C.c_uint],
     }
     for name, args in sig.items():
         fn = getattr(l, name)

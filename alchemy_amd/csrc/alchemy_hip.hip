@@ -502,6 +502,75 @@ __global__ void k_ct_tensor3(DevRing<W> R, const W* a, const W* b, W* out, size_
     }
 }
 
+// SymmSHE (+), (-) and negate on operands that are not aligned (alch_ct_add): out_i = fa * a_i + fb * b_i for every component i, with
+// one combined factor per operand, f = g^d * s -- the g-power that brings the operand to the common k and the per-limb scalar that
+// carries its encoding change and Z_p scalar.  sa, sb = s R (Montgomery; read only when bit 0 / bit 1 of `scaled`
+// is set), gt = the CRT image of g in Montgomery form (all-null where g = 1: the powers are then ignored), ga, gb = the powers.
+// DA, DB = the operands' degrees, DB = 0: no second operand (negate, mulG or an encoding change of a whole ciphertext).  A
+// ciphertext of degree d is elements (d + 1) ct .. (d + 1) ct + d; out has degree max(DA, DB), and a c2 that only one operand has
+// is scaled and stored, never summed with a zero.  Every word of out is read (from whichever operand out aliases) and written by
+// the same lane, so out may be a or b when that operand has the result's degree.
+template <typename W>
+__device__ inline W ct_add_factor(W gw, u32 d, bool has_s, W s, const ModP<W>& m) {
+    if (d == 0) return s;                                   // the caller asks only when d > 0 or has_s
+    W f = gw;                                               // g R
+    for (u32 i = 1; i < d; ++i) f = mont_mul(f, gw, m);     // g^d R
+    return has_s ? mont_mul(f, s, m) : f;                   // g^d s R
+}
+
+template <typename W, int VW, int DA, int DB>
+__global__ void k_ct_add(DevRing<W> R, const W* a, const W* b, W* out, size_t nct, Scal<W> sa, Scal<W> sb, GTab<W> gt, u32 ga, u32 gb,
+                         u32 scaled) {
+    typedef Pack<W, VW> P;
+    constexpr int DO = DA > DB ? DA : DB, DS = DA < DB ? DA : DB;
+    const size_t n = (size_t)R.n, Ln = (size_t)R.L * n;
+    ALCH_WALK_INIT(R.n / VW, R.L);
+    ALCH_WALK(w, nct * Ln / VW, wk) {
+        const size_t ct = wk.outer, rem = (size_t)wk.mid * n + (size_t)wk.k * VW;
+        const ModP<W> m = R.mod[wk.mid];
+        const W* g = (ga | gb) ? gt.p[wk.mid] : nullptr;
+        P gv;
+        if (g) gv = *reinterpret_cast<const P*>(g + (size_t)wk.k * VW);
+        const u32 da = g ? ga : 0u, db = g ? gb : 0u;
+        const bool has_sa = (scaled & 1u) != 0, has_sb = (scaled & 2u) != 0;
+        P x[DO + 1];
+        const W* pa = a + (size_t)(DA + 1) * ct * Ln + rem;
+#pragma unroll
+        for (int i = 0; i <= DA; ++i) x[i] = *reinterpret_cast<const P*>(pa + (size_t)i * Ln);
+        if (da || has_sa) {
+#pragma unroll
+            for (int c = 0; c < VW; ++c) {
+                const W f = ct_add_factor<W>(g ? gv.v[c] : (W)0, da, has_sa, sa.v[wk.mid], m);
+#pragma unroll
+                for (int i = 0; i <= DA; ++i) x[i].v[c] = mont_mul(x[i].v[c], f, m);
+            }
+        }
+        if constexpr (DB > 0) {
+            P y[DB + 1];
+            const W* pb = b + (size_t)(DB + 1) * ct * Ln + rem;
+#pragma unroll
+            for (int i = 0; i <= DB; ++i) y[i] = *reinterpret_cast<const P*>(pb + (size_t)i * Ln);
+            if (db || has_sb) {
+#pragma unroll
+                for (int c = 0; c < VW; ++c) {
+                    const W f = ct_add_factor<W>(g ? gv.v[c] : (W)0, db, has_sb, sb.v[wk.mid], m);
+#pragma unroll
+                    for (int i = 0; i <= DB; ++i) y[i].v[c] = mont_mul(y[i].v[c], f, m);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i <= DS; ++i)
+#pragma unroll
+                for (int c = 0; c < VW; ++c) x[i].v[c] = add_mod(x[i].v[c], y[i].v[c], m.q);
+#pragma unroll
+            for (int i = DA + 1; i <= DB; ++i) x[i] = y[i];
+        }
+        W* o = out + (size_t)(DO + 1) * ct * Ln + rem;
+#pragma unroll
+        for (int i = 0; i <= DO; ++i) *reinterpret_cast<P*>(o + (size_t)i * Ln) = x[i];
+    }
+}
+
 // The way into keySwitchQuadCirc as a step of its own (alch_ct_key_switch_quad): the components of `nct` quadratic ciphertexts
 // (elements 3 ct ..) times toMSD's scalar (sm = s R; scale = 0: s = 1, plain copies): (c0, c1) -> pair [ct][2], c2 -> c2a [ct] and,
 // when given, a second copy c2b (the one that stays in the CRT basis).
@@ -2910,6 +2979,112 @@ extern "C" int alch_ct_mul(alch_ring* r, const alch_buf* a, const alch_buf* b, a
     if (batch == 0) return ALCH_OK;
     BIND(r);
     return ALCH_BY_WORD(r, do_ct_mul, r, a->dptr, b->dptr, out->dptr, batch, s_pre, flags);
+} catch (...) { return abi_catch(); }
+
+// ---- SymmSHE (+), (-), negate on resident batches, operands unaligned (within ABI 1.8; a host probes for the symbol) -------------------
+// add_ = pureE (+) and neg_ = pureE negate (Eval.hs:59-60, PT2CT.hs:117-118).  SymmSHE's (+) owes its operands an alignment -- the
+// g-power k, the Z_p scalar l, the MSD / LSD encoding, the degree -- and all of it is per-limb scalars and powers of the CRT image
+// of g: one element-wise pass (k_ct_add), the metadata rule on the host (alchemy_amd/ctadd.py: align).
+// The pack width follows ALCH_LAUNCH_VW's rule (that macro names kernels of two template parameters; this one has four).
+template <typename W, int DA, int DB>
+static int launch_ct_add(alch_ring* r, const W* a, const W* b, W* out, size_t nct, const Scal<W>& sa, const Scal<W>& sb,
+                         const GTab<W>& gt, u32 ga, u32 gb, u32 scaled) {
+    constexpr int VL = Vec4<W>::LANES;
+    const size_t items = nct * elem_words(r);
+    if (r->n % VL == 0)
+        hipLaunchKernelGGL((k_ct_add<W, VL, DA, DB>), dim3(ew_grid(items / VL)), dim3(256), 0, r->stream, dev_ring<W>(r), a, b, out, nct,
+                           sa, sb, gt, ga, gb, scaled);
+    else
+        hipLaunchKernelGGL((k_ct_add<W, 1, DA, DB>), dim3(ew_grid(items)), dim3(256), 0, r->stream, dev_ring<W>(r), a, b, out, nct,
+                           sa, sb, gt, ga, gb, scaled);
+    HIP_TRY(hipGetLastError());
+    return ALCH_OK;
+}
+
+template <typename W>
+static int do_ct_add(alch_ring* r, void* out, size_t batch, const void* a, int deg_a, const uint64_t* s_a, unsigned g_a,
+                     const void* b, int deg_b, const uint64_t* s_b, unsigned g_b, bool pow_basis) {
+    // deg_b = 0: no second operand
+    Scal<W> sa, sb;
+    scal_to_mont<W>(r, s_a, 1, sa);
+    scal_to_mont<W>(r, s_b, 1, sb);
+    const u32 scaled = (s_a ? 1u : 0u) | (s_b ? 2u : 0u);
+    const bool has_g = r->gen && r->gh.rad > 1;                        // otherwise g = 1 and its powers are the identity
+    if (!has_g) g_a = g_b = 0;
+    const size_t eb = elem_bytes(r), ew = elem_words(r);
+    const size_t ea = (size_t)deg_a + 1, ebb = (size_t)deg_b + 1, eo = (size_t)std::max(deg_a, deg_b) + 1;
+    // Pow basis, general index: g is no pointwise factor there.  The operand that needs it goes through the batched mulG column
+    // operator into the ring's scratch, chunk by chunk, and the pass reads it from there with no g-power left.
+    const bool col_a = pow_basis && g_a, col_b = pow_basis && deg_b && g_b;
+    size_t chunk = batch;
+    if (col_a || col_b) {
+        const size_t per_ct = ((col_a ? ea : 0) + (col_b ? ebb : 0)) * eb;
+        chunk = std::min(batch, std::max<size_t>(1, (r->scratch_mib << 20) / per_ct));
+        if (int rc = ensure_ws(&r->ws_in, &r->ws_in_bytes, chunk * per_ct)) return rc;
+    }
+    const GTab<W> gt = pow_basis ? GTab<W>{} : g_table<W>(r);
+    const u32 ka = pow_basis ? 0u : g_a, kb = pow_basis ? 0u : g_b;
+    for (size_t done = 0; done < batch; done += chunk) {
+        const size_t now = std::min(chunk, batch - done);
+        const W* pa = reinterpret_cast<const W*>(a) + done * ea * ew;
+        const W* pb = deg_b ? reinterpret_cast<const W*>(b) + done * ebb * ew : nullptr;
+        char* ws = reinterpret_cast<char*>(r->ws_in);
+        if (col_a) {
+            for (unsigned t = 0; t < g_a; ++t)
+                if (int rc = do_columns<W>(r, GEN_MULG_POW, ws, 0, now * ea, 1, nullptr, t == 0 ? pa : nullptr)) return rc;
+            pa = reinterpret_cast<const W*>(ws);
+            ws += now * ea * eb;
+        }
+        if (col_b) {
+            for (unsigned t = 0; t < g_b; ++t)
+                if (int rc = do_columns<W>(r, GEN_MULG_POW, ws, 0, now * ebb, 1, nullptr, t == 0 ? pb : nullptr)) return rc;
+            pb = reinterpret_cast<const W*>(ws);
+        }
+        W* po = reinterpret_cast<W*>(out) + done * eo * ew;
+        int rc;
+        switch (deg_a * 3 + deg_b) {
+        case 3: rc = launch_ct_add<W, 1, 0>(r, pa, pb, po, now, sa, sb, gt, ka, kb, scaled); break;
+        case 4: rc = launch_ct_add<W, 1, 1>(r, pa, pb, po, now, sa, sb, gt, ka, kb, scaled); break;
+        case 5: rc = launch_ct_add<W, 1, 2>(r, pa, pb, po, now, sa, sb, gt, ka, kb, scaled); break;
+        case 6: rc = launch_ct_add<W, 2, 0>(r, pa, pb, po, now, sa, sb, gt, ka, kb, scaled); break;
+        case 7: rc = launch_ct_add<W, 2, 1>(r, pa, pb, po, now, sa, sb, gt, ka, kb, scaled); break;
+        default: rc = launch_ct_add<W, 2, 2>(r, pa, pb, po, now, sa, sb, gt, ka, kb, scaled); break;
+        }
+        if (rc != ALCH_OK) return rc;
+    }
+    return ALCH_OK;
+}
+
+extern "C" int alch_ct_add(alch_buf* out, size_t batch, const alch_buf* a, int deg_a, const uint64_t* s_a, unsigned g_a,
+                           const alch_buf* b, int deg_b, const uint64_t* s_b, unsigned g_b, unsigned flags) try {
+    if (!out || !a) return fail(ALCH_E_INVALID, "alch_ct_add: null buffer");
+    alch_ring* r = out->ring;
+    if (a->ring != r || (b && b->ring != r)) return fail(ALCH_E_INVALID, "alch_ct_add: buffers belong to different rings");
+    if (!b) { deg_b = 0; s_b = nullptr; g_b = 0; }                     // the unary form ignores them
+    if ((deg_a != 1 && deg_a != 2) || (b && deg_b != 1 && deg_b != 2)) return fail(ALCH_E_INVALID, "alch_ct_add: degree must be 1 or 2");
+    if (flags & ~(unsigned)(ALCH_POW_IN | ALCH_POW_OUT)) return fail(ALCH_E_INVALID, "alch_ct_add: unknown flag");
+    if (g_a > 16 || g_b > 16) return fail(ALCH_E_INVALID, "alch_ct_add: a g-power above 16");
+    const size_t ea = (size_t)deg_a + 1, ebb = (size_t)deg_b + 1, eo = std::max(ea, ebb);
+    if (batch > a->n_elems / ea || (b && batch > b->n_elems / ebb) || batch > out->n_elems / eo)
+        return fail(ALCH_E_INVALID, "alch_ct_add: a buffer holds fewer than (degree + 1) * batch ring elements");
+    // out may BE an operand of the result's degree (every word is read and written by one lane); any other overlap is refused
+    const size_t eby = elem_bytes(r);
+    auto alias_ok = [&](const alch_buf* x, size_t ex) {
+        if (out->dptr == x->dptr) return ex == eo;
+        return !bytes_overlap(out->dptr, eo * batch * eby, x->dptr, ex * batch * eby);
+    };
+    if (!alias_ok(a, ea) || (b && !alias_ok(b, ebb)))
+        return fail(ALCH_E_INVALID, "alch_ct_add: out overlaps an operand without being that operand at the result's degree");
+    const bool pow_basis = (flags & ALCH_POW_IN) != 0;
+    if (pow_basis != ((flags & ALCH_POW_OUT) != 0))
+        return fail(ALCH_E_UNSUPPORTED, "alch_ct_add: one basis in and out (0 or ALCH_POW_IN | ALCH_POW_OUT); alch_buf_crt / alch_buf_crtinv change it");
+    if (!r->has_crt) {
+        if (!pow_basis && (g_a || g_b)) return fail(ALCH_E_NO_CRT, "alch_ct_add: a g-power on the CRT basis of a ring that has none");
+        return fail(ALCH_E_UNSUPPORTED, "scalar products are implemented for rings with Montgomery constants (prime moduli) only");
+    }
+    if (batch == 0) return ALCH_OK;
+    BIND(r);
+    return ALCH_BY_WORD(r, do_ct_add, r, out->dptr, batch, a->dptr, deg_a, s_a, g_a, b ? b->dptr : nullptr, deg_b, s_b, g_b, pow_basis);
 } catch (...) { return abi_catch(); }
 
 // keySwitchQuadCirc from a resident quadratic ciphertext, through the composed stage (ks_stage with a ready c2).  Per chunk:

@@ -138,6 +138,8 @@ foreign import ccall safe   "alch_ct_mul_full"         c_ctMulFull       :: Ptr 
 foreign import ccall safe   "alch_ct_mul"              c_ctMul           :: Ptr AlchRing -> Ptr AlchBuf -> Ptr AlchBuf -> Ptr AlchBuf -> CSize -> Ptr Word64 -> CUInt -> IO CInt
 foreign import ccall safe   "alch_ct_key_switch_quad"  c_ctKeySwitchQuad :: Ptr AlchHint -> Ptr AlchBuf -> Ptr AlchBuf -> CSize -> Ptr Word64 -> CUInt -> IO CInt
 foreign import ccall safe   "alch_ct_mod_switch_deg"   c_ctModSwitchDeg  :: Ptr AlchBuf -> Ptr AlchBuf -> CSize -> CInt -> CUInt -> IO CInt
+-- SymmSHE (+), (-), negate on resident batches with unaligned operands (added within library version 1.8): s_a g^g_a a + s_b g^g_b b
+foreign import ccall safe   "alch_ct_add"              c_ctAdd           :: Ptr AlchBuf -> CSize -> Ptr AlchBuf -> CInt -> Ptr Word64 -> CUInt -> Ptr AlchBuf -> CInt -> Ptr Word64 -> CUInt -> CUInt -> IO CInt
 -- plaintext ring elements on resident batches (added within library version 1.8): E's mul_, div2_, linearCyc_ and addLit_ on `Cyc t m zp`
 -- over a lifting ring; the linear-function handle is an opaque pointer
 foreign import ccall safe   "alch_pt_bound"            c_ptBound         :: Word32 -> Word64 -> Word32 -> Ptr Word64 -> Ptr Word64 -> IO CInt

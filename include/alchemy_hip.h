@@ -84,7 +84,8 @@ const char *alch_last_error(void);
 /* Library/ABI version: (major<<16)|minor; the minor number goes up with every added capability (1.7: tunnels between two-power rings; 1.8: decrypt / error rates on resident batches).).
  * The step entry points of mul_ (alch_ct_mul, alch_ct_key_switch_quad, alch_ct_mod_switch_deg) were added WITHIN 1.8 -- the number did
  * not move; a host that wants them probes for the symbols (dlsym / ctypes hasattr).  So were the plaintext-side entry points
- * (alch_pt_mul, alch_pt_linear_create / _free, alch_pt_eval_lin, alch_pt_rescale, alch_buf_add_bcast, alch_pt_bound). */
+ * (alch_pt_mul, alch_pt_linear_create / _free, alch_pt_eval_lin, alch_pt_rescale, alch_buf_add_bcast, alch_pt_bound) and
+ * alch_ct_add. */
 uint32_t alch_version(void);
 
 /* ---- ring context ------------------------------------------------------------------------------
@@ -451,6 +452,30 @@ int alch_ct_key_switch_quad(const alch_hint *hint, const alch_buf *in, alch_buf 
  * degree 1 gives alch_ct_mod_switch's results word for word.  Two rings on different streams are ordered as alch_ct_mod_switch
  * orders them. */
 int alch_ct_mod_switch_deg(const alch_buf *in, alch_buf *out, size_t batch, int degree, unsigned flags);
+
+/* ---- SymmSHE (+), (-), negate on resident batches, operands unaligned (added within 1.8; probe for the symbol) --------------
+ * add_ = pureE (+) and neg_ = pureE negate on ciphertexts (Eval.hs:59-60, PT2CT.hs:117-118).  SymmSHE's (+) aligns its operands
+ * first: the g-power k (mulG on the operand with the smaller k), the Z_p scalar l, the MSD / LSD encoding, and the degree (a
+ * quadratic ciphertext before its key switch plus a linear one).  Every one of these is a per-limb scalar or a power of g, so a
+ * whole unaligned sum is ONE element-wise pass:
+ *       out[ct] = s_a * g^g_a * a[ct]  +  s_b * g^g_b * b[ct]        component by component, mod q_j
+ * The (enc, k, l, degree) metadata stays on the host, as for alch_ct_mul; alchemy_amd/ctadd.py (`align`) turns two metadata
+ * records into (s_a, g_a, s_b, g_b) by the rule of DESIGN section 16 -- subtraction and negate are the scalar's sign.
+ *   layouts  a ciphertext of degree d is elements (d + 1) ct .. (d + 1) ct + d (alch_ct_mul's layout for d = 2); deg_a, deg_b in
+ *            {1, 2}; out has degree max(deg_a, deg_b).  A c2 that only one operand has is scaled and stored as it is.
+ *   s_x      L plain residues (reduced mod q_j like alch_buf_scale's), NULL = 1.   g_x <= 16; ignored where g = 1 (two-power index).
+ *   b NULL   the unary form out = s_a * g^g_a * a (deg_b, s_b, g_b ignored): negate, mulG or toMSD / toLSD of whole ciphertexts.
+ *   flags    0: CRT basis in and out (g^d is a pointwise factor read from the ring's table).  ALCH_POW_IN | ALCH_POW_OUT: Pow basis
+ *            in and out; on a general index an operand with a non-zero g-power first goes through the batched mulG of the Pow basis
+ *            into the ring's scratch, in chunks of at most "scratch_mib".  One flag alone: ALCH_E_UNSUPPORTED (alch_buf_crt exists).
+ *   aliasing out may BE a or b when that operand has the result's degree; any other overlap is ALCH_E_INVALID.  a may be b.
+ * Statuses, in this order: ALCH_E_INVALID (null out or a; buffers of different rings; a degree outside {1, 2}; unknown flag;
+ * g_x > 16; a buffer smaller than (degree + 1) * batch; overlap), ALCH_E_UNSUPPORTED (one basis flag alone), ALCH_E_NO_CRT (a ring
+ * from alch_ring_create_nocrt asked for a g-power on the CRT basis; such a ring is ALCH_E_UNSUPPORTED otherwise, as for
+ * alch_buf_scale), device errors last.  batch = 0: ALCH_OK, nothing launched.  All three buffers belong to one ring, so the work
+ * is ordered by that ring's stream alone. */
+int alch_ct_add(alch_buf *out, size_t batch, const alch_buf *a, int deg_a, const uint64_t *s_a, unsigned g_a,
+                const alch_buf *b, int deg_b, const uint64_t *s_b, unsigned g_b, unsigned flags);
 
 /* ---- decrypt and errorRate_ on resident ciphertext batches (since 1.8) -------------------------------------------------
  * SymmSHE decrypt (Crypto/Alchemy/Interpreter/PT2CT.hs:91-99) and errorTermUnrestricted as the ErrorRateWriter interpreter logs it
