@@ -41,6 +41,7 @@ SYMBOLS = [
     "alch_pt_bound", "alch_pt_mul", "alch_pt_linear_create", "alch_pt_linear_free", "alch_pt_eval_lin", "alch_pt_rescale",
     "alch_buf_add_bcast",
     "alch_ct_add",
+    "alch_gauss_table", "alch_gauss_plan", "alch_buf_gauss_dec", "alch_ct_encrypt",
 ]
 
 
@@ -175,6 +176,10 @@ def load_library():
         "alch_pt_rescale": [VP, VP, C.c_size_t],
         "alch_buf_add_bcast": [VP, VP, VP, C.c_size_t, C.c_size_t],
         "alch_ct_add": [VP, C.c_size_t, VP, C.c_int, PU64, C.c_uint, VP, C.c_int, PU64, C.c_uint, C.c_uint],
+        "alch_gauss_table": [PU64, C.POINTER(C.c_size_t)],
+        "alch_gauss_plan": [C.c_uint32, C.c_uint64, PU64, PU64, C.POINTER(C.c_size_t)],
+        "alch_buf_gauss_dec": [VP, C.c_size_t, C.c_size_t, C.c_uint64, VP, C.c_size_t, C.c_uint64, C.c_uint64],
+        "alch_ct_encrypt": [VP, C.c_size_t, VP, C.c_size_t, VP, C.c_size_t, C.c_uint64, C.c_uint64],
     }
     for name, args in sig.items():
         fn = getattr(l, name)

@@ -88,6 +88,8 @@ struct alch_ring {
     size_t ws_lift_bytes = 0;
     void* ws_maxd = nullptr;                   // digit vectors of max |lift|, 8 L bytes per element
     size_t ws_maxd_bytes = 0;
+    void* ws_gauss = nullptr;                  // alch_buf_gauss_dec on an index with odd primes: the doubles of one chunk of elements
+    size_t ws_gauss_bytes = 0;
     int device = 0;                            // HIP device the ring's streams, tables and buffers live on
     LaunchOpts opts;                           // launch-structure options (alch_ring_set_option)
     bool one_stream = false;
@@ -1284,6 +1286,7 @@ __global__ void k_checksum(const W* data, size_t words, u64* sum, u64 w0) {
 
 #include "kernel_lift.hpp"
 #include "kernel_plain.hpp"
+#include "kernel_rlwe.hpp"
 
 static inline unsigned ew_grid(size_t items) {
     size_t g = (items + 255) / 256;
@@ -1627,6 +1630,7 @@ extern "C" int alch_ring_destroy(alch_ring* r) try {
     if (r->ws_full) (void)hipFree(r->ws_full);
     if (r->ws_lift) (void)hipFree(r->ws_lift);
     if (r->ws_maxd) (void)hipFree(r->ws_maxd);
+    if (r->ws_gauss) (void)hipFree(r->ws_gauss);
     if (r->ev_x) (void)hipEventDestroy(r->ev_x);
     if (r->ws_host) (void)hipFree(r->ws_host);
     if (r->ws_sum) (void)hipFree(r->ws_sum);
@@ -4184,6 +4188,159 @@ extern "C" int alch_ct_decrypt_lift(const alch_buf* in, size_t batch, int degree
     if (rc != ALCH_OK) return rc;
     if (rd && (rc = ext_order(r, rd, false)) != ALCH_OK) return rc;
     return maxd_fetch(r, max_digits, batch);
+} catch (...) { return abi_catch(); }
+
+// ------------------------------------------------------------------------------------------------------
+// encrypt on resident batches: the counter-based Gaussian on the decoding basis and SymmSHE encrypt's ring arithmetic (kernel_rlwe.hpp)
+// ------------------------------------------------------------------------------------------------------
+static inline double bits_to_double(uint64_t b) { double d; memcpy(&d, &b, sizeof d); return d; }
+static inline uint64_t double_to_bits(double d) { uint64_t b; memcpy(&b, &d, sizeof b); return b; }
+
+extern "C" int alch_gauss_table(uint64_t* cdt, size_t* len) try {
+    if (!len) return fail(ALCH_E_INVALID, "alch_gauss_table: null len");
+    if (cdt) {
+        if (*len < gauss::CDT_LEN) return fail(ALCH_E_INVALID, "alch_gauss_table: the array is shorter than the table (query with cdt = NULL)");
+        memcpy(cdt, gauss::CDT, sizeof gauss::CDT);
+    }
+    *len = gauss::CDT_LEN;
+    return ALCH_OK;
+} catch (...) { return abi_catch(); }
+
+extern "C" int alch_gauss_plan(uint32_t m, uint64_t svar_bits, uint64_t* scale_bits, uint64_t* chol_bits, size_t* chol_len) try {
+    if (m < 1) return fail(ALCH_E_INVALID, "alch_gauss_plan: cyclotomic index must be >= 1");
+    if (!gauss::svar_ok(bits_to_double(svar_bits))) return fail(ALCH_E_INVALID, "alch_gauss_plan: svar must be finite and positive");
+    if (chol_bits && !chol_len) return fail(ALCH_E_INVALID, "alch_gauss_plan: chol_bits needs chol_len");
+    const gauss::Plan P = gauss::make_plan(m, bits_to_double(svar_bits));
+    size_t need = 0;
+    for (const gauss::Axis& a : P.axes) need += a.Lc.size();
+    if (chol_bits) {
+        if (*chol_len < need) return fail(ALCH_E_INVALID, "alch_gauss_plan: the array is shorter than the factors (query with chol_bits = NULL)");
+        size_t at = 0;
+        for (const gauss::Axis& a : P.axes)
+            for (double v : a.Lc) chol_bits[at++] = double_to_bits(v);
+    }
+    if (chol_len) *chol_len = need;
+    if (scale_bits) *scale_bits = double_to_bits(P.scale);
+    return ALCH_OK;
+} catch (...) { return abi_catch(); }
+
+static void launch_gauss_axis(hipStream_t st, const gauss::Axis& a, double* xs, u32 n, u32 cols) {
+    GaussChol C;
+    memset(&C, 0, sizeof C);
+    memcpy(C.l, a.Lc.data(), a.Lc.size() * sizeof(double));
+    const dim3 g(ew_grid(cols)), b(256);
+    switch (a.p) {
+        case 3: hipLaunchKernelGGL((k_gauss_axis<3>), g, b, 0, st, C, xs, n, a.mp, a.stride, cols); break;
+        case 5: hipLaunchKernelGGL((k_gauss_axis<5>), g, b, 0, st, C, xs, n, a.mp, a.stride, cols); break;
+        case 7: hipLaunchKernelGGL((k_gauss_axis<7>), g, b, 0, st, C, xs, n, a.mp, a.stride, cols); break;
+        case 11: hipLaunchKernelGGL((k_gauss_axis<11>), g, b, 0, st, C, xs, n, a.mp, a.stride, cols); break;
+        default: hipLaunchKernelGGL((k_gauss_axis<13>), g, b, 0, st, C, xs, n, a.mp, a.stride, cols); break;
+    }
+}
+
+// `count` elements at dst (limb-major words of r), coset: the Z_p words of the first element or null.
+template <typename W>
+static int do_gauss_dec(alch_ring* r, const gauss::Plan& P, void* dst, size_t count, u32 p, const u32* coset, uint64_t seed, uint64_t elem0) {
+    GaussPar G;
+    memset(&G, 0, sizeof G);
+    for (int j = 0; j < r->L; ++j) G.q[j] = r->q[j];
+    G.seed = seed; G.scale = P.scale; G.L = (u32)r->L; G.n = r->n; G.p = p;
+    const size_t n = r->n;
+    if (P.axes.empty()) {                                              // two-power index: one kernel, no scratch
+        while (((u32)1 << G.logn) < r->n) ++G.logn;
+        G.ctr0 = elem0 * (u64)n;
+        const size_t total = count * n;
+        hipLaunchKernelGGL((k_gauss_sample<W, true>), dim3(ew_grid(total)), dim3(256), 0, r->stream, G, (double*)nullptr,
+                           reinterpret_cast<W*>(dst), coset, total);
+        HIP_TRY(hipGetLastError());
+        return ALCH_OK;
+    }
+    // scratch of one chunk: at most 1 GiB and fewer than 2^31 coefficients (2^27 doubles)
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(count, ((size_t)1 << 27) / n));
+    if (int rc = ensure_ws(&r->ws_gauss, &r->ws_gauss_bytes, chunk * n * sizeof(double))) return rc;
+    double* xs = reinterpret_cast<double*>(r->ws_gauss);
+    for (size_t done = 0; done < count; done += chunk) {
+        const size_t now = std::min(chunk, count - done);
+        const u32 total = (u32)(now * n);
+        G.ctr0 = (elem0 + (u64)done) * (u64)n;
+        hipLaunchKernelGGL((k_gauss_sample<W, false>), dim3(ew_grid(total)), dim3(256), 0, r->stream, G, xs, (W*)nullptr,
+                           (const u32*)nullptr, (size_t)total);
+        for (const gauss::Axis& a : P.axes) launch_gauss_axis(r->stream, a, xs, r->n, total / (a.p - 1));
+        hipLaunchKernelGGL((k_gauss_round<W>), dim3(ew_grid(total)), dim3(256), 0, r->stream, G, xs,
+                           reinterpret_cast<W*>(dst) + done * elem_words(r), coset ? coset + done * n : nullptr, total);
+        HIP_TRY(hipGetLastError());
+    }
+    return ALCH_OK;
+}
+
+extern "C" int alch_buf_gauss_dec(alch_buf* dst, size_t first, size_t count, uint64_t svar_bits, const alch_buf* coset_zp,
+                                  size_t coset_first, uint64_t seed, uint64_t elem0) try {
+    if (!dst) return fail(ALCH_E_INVALID, "alch_buf_gauss_dec: null buffer");
+    alch_ring* r = dst->ring;
+    BIND(r);
+    const double svar = bits_to_double(svar_bits);
+    if (!gauss::svar_ok(svar)) return fail(ALCH_E_INVALID, "alch_buf_gauss_dec: svar must be finite and positive");
+    if (!range_ok(first, count, dst->n_elems)) return fail(ALCH_E_INVALID, "alch_buf_gauss_dec: element range out of bounds");
+    u32 p = 0;
+    if (coset_zp) {
+        const alch_ring* rc = coset_zp->ring;
+        if (rc->m != r->m || rc->n != r->n) return fail(ALCH_E_INVALID, "alch_buf_gauss_dec: the coset ring must have the destination's cyclotomic index");
+        if (rc->L != 1 || rc->zdom || rc->word != 4 || rc->q[0] < 2 || rc->q[0] >= ((u64)1 << 31))
+            return fail(ALCH_E_INVALID, "alch_buf_gauss_dec: the coset ring must have exactly one modulus 2 <= p < 2^31");
+        if (rc->device != r->device) return fail(ALCH_E_INVALID, "alch_buf_gauss_dec: the rings live on different devices");
+        if (!range_ok(coset_first, count, coset_zp->n_elems)) return fail(ALCH_E_INVALID, "alch_buf_gauss_dec: coset range out of bounds");
+        p = (u32)rc->q[0];
+    }
+    const gauss::Plan P = gauss::make_plan(r->m, svar);
+    if (P.n != r->n) return fail(ALCH_E_INTERNAL, "alch_buf_gauss_dec: ring dimension mismatch");
+    for (const gauss::Axis& a : P.axes)
+        if (a.p > gauss::MAX_ODD_PRIME) return fail(ALCH_E_UNSUPPORTED, "alch_buf_gauss_dec: odd primes of the index up to 13 are served");
+    if (!gauss::bound_ok(P, p)) return fail(ALCH_E_INVALID, "alch_buf_gauss_dec: svar is too large: the rounded coefficients would not stay below 2^62");
+    if (count == 0) return ALCH_OK;
+    char* d = reinterpret_cast<char*>(dst->dptr) + first * elem_bytes(r);
+    const u32* cs = nullptr;
+    if (coset_zp) {
+        cs = reinterpret_cast<const u32*>(coset_zp->dptr) + coset_first * (size_t)r->n;
+        // the coset in the destination itself (a one-modulus 32-bit ring): in place is fine -- a lane reads its word before it writes it -- shifted is not
+        if ((const void*)cs != (const void*)d && bytes_overlap(d, count * elem_bytes(r), cs, count * (size_t)r->n * 4))
+            return fail(ALCH_E_INVALID, "alch_buf_gauss_dec: overlapping ranges");
+    }
+    alch_ring* rc = coset_zp ? coset_zp->ring : nullptr;
+    int rcode;
+    if (rc && (rcode = ext_order(r, rc, true)) != ALCH_OK) return rcode;
+    if ((rcode = ALCH_BY_WORD(r, do_gauss_dec, r, P, d, count, p, cs, seed, elem0)) != ALCH_OK) return rcode;
+    if (rc && (rcode = ext_order(r, rc, false)) != ALCH_OK) return rcode;
+    return ALCH_OK;
+} catch (...) { return abi_catch(); }
+
+template <typename W>
+static int do_ct_encrypt(alch_ring* r, void* out, size_t batch, const void* err, const void* sk, uint64_t seed, uint64_t ct0) {
+    const DevRing<W>& R = dev_ring<W>(r);
+    const size_t words = batch * elem_words(r);
+    W* o = reinterpret_cast<W*>(out);
+    const W *e = reinterpret_cast<const W*>(err), *s = reinterpret_cast<const W*>(sk);
+    ALCH_LAUNCH_VW(k_ct_encrypt, r, words, r->stream, R, o, e, s, words, seed, ct0);
+    HIP_TRY(hipGetLastError());
+    return ALCH_OK;
+}
+
+extern "C" int alch_ct_encrypt(alch_buf* out, size_t batch, const alch_buf* err_crt, size_t err_first, const alch_buf* sk_crt,
+                               size_t sk_index, uint64_t seed, uint64_t ct0) try {
+    if (!out || !err_crt || !sk_crt) return fail(ALCH_E_INVALID, "alch_ct_encrypt: null buffer");
+    alch_ring* r = out->ring;
+    BIND(r);
+    if (err_crt->ring != r || sk_crt->ring != r) return fail(ALCH_E_INVALID, "alch_ct_encrypt: the error terms and the key must belong to the output's ring");
+    if (!pairs_ok(batch, out->n_elems)) return fail(ALCH_E_INVALID, "alch_ct_encrypt: the output must hold 2 * batch ring elements");
+    if (!range_ok(err_first, batch, err_crt->n_elems)) return fail(ALCH_E_INVALID, "alch_ct_encrypt: error-term range out of bounds");
+    if (sk_index >= sk_crt->n_elems) return fail(ALCH_E_INVALID, "alch_ct_encrypt: key index out of bounds");
+    if (!r->has_crt) return fail(ALCH_E_NO_CRT, "alch_ct_encrypt: this ring has no CRT basis (created with alch_ring_create_nocrt)");
+    if (batch == 0) return ALCH_OK;
+    const size_t eb = elem_bytes(r);
+    const void* e = reinterpret_cast<const char*>(err_crt->dptr) + err_first * eb;
+    const void* sk = reinterpret_cast<const char*>(sk_crt->dptr) + sk_index * eb;
+    if (bytes_overlap(out->dptr, 2 * batch * eb, e, batch * eb) || bytes_overlap(out->dptr, 2 * batch * eb, sk, eb))
+        return fail(ALCH_E_INVALID, "alch_ct_encrypt: the output overlaps an input");
+    return ALCH_BY_WORD(r, do_ct_encrypt, r, out->dptr, batch, e, sk, seed, ct0);
 } catch (...) { return abi_catch(); }
 
 // ------------------------------------------------------------------------------------------------------

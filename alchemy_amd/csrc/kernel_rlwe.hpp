@@ -1,0 +1,119 @@
+// encrypt on resident batches (include/alchemy_hip.h, "encrypt"): the kernels behind alch_buf_gauss_dec and alch_ct_encrypt.
+// Included from alchemy_hip.hip after the element-wise helpers (Walk3, Pack, ALCH_WALK) it uses; the arithmetic of one coefficient
+// is gauss_sampler.hpp's, shared with the host.
+//
+//   k_gauss_sample    one lane per coefficient: counter -> two splitmix64 words -> table search in LDS -> (double)f * scale.
+//                     FUSED (two-power index: no odd axis): rounds and stores the residues of every limb at once, no scratch
+//   k_gauss_axis<P>   the Cholesky factor of P I - J along one odd axis of the scratch: one lane per column, column in registers
+//   k_gauss_round     scratch doubles -> (coset) rounding -> residues of every limb, limb-major
+//   k_ct_encrypt      c1 = the uniform words of alch_buf_fill_uniform's odd elements, c0 = err - c1 s, one pass on the CRT basis
+#pragma once
+
+#include "gauss_sampler.hpp"
+
+namespace alch {
+
+__device__ const u64 d_gauss_cdt[gauss::CDT_LEN] = {ALCH_GAUSS_CDT_VALUES};
+
+struct GaussPar {
+    u64 q[MAXL];               // destination moduli (0: the integers)
+    u64 seed, ctr0;            // stream, counter of coefficient 0 of the launch's first element: (elem0 + e0) n mod 2^64
+    double scale;
+    u32 L, n, logn;            // logn: only read by the fused kernel (n a power of two)
+    u32 p;                     // coset modulus, 0 = errorRounded
+};
+
+// The table, once per workgroup: 582 words, 4.7 KiB of LDS.
+__device__ __forceinline__ void gauss_load_cdt(u64* T) {
+    for (u32 i = threadIdx.x; i < gauss::CDT_LEN; i += blockDim.x) T[i] = d_gauss_cdt[i];
+    __syncthreads();
+}
+
+// total = coefficients of the launch (elements * n).  FUSED: dst = limb-major words of the first element, coset (nullable) = the
+// Z_p words of the first element; otherwise xs = scratch doubles, dst and coset unused.
+template <typename W, bool FUSED>
+__global__ void __launch_bounds__(256) k_gauss_sample(GaussPar G, double* xs, W* dst, const u32* coset, size_t total) {
+    __shared__ u64 T[gauss::CDT_LEN];
+    gauss_load_cdt(T);
+    for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        const double x = gauss::sample(G.seed, G.ctr0 + (u64)idx, G.scale, T);
+        if (!FUSED) { xs[idx] = x; continue; }
+        const int64_t z = gauss::round_coset(x, G.p, G.p ? coset[idx] : 0u);
+        const size_t e = idx >> G.logn, i = idx & ((size_t)G.n - 1);
+        W* o = dst + (e * G.L) * (size_t)G.n + i;
+#pragma unroll
+        for (int j = 0; j < MAXL; ++j)
+            if ((u32)j < G.L) o[(size_t)j * G.n] = (W)gauss::reduce(z, G.q[j]);
+    }
+}
+
+struct GaussChol { double l[(gauss::MAX_ODD_PRIME - 1) * (gauss::MAX_ODD_PRIME - 1)]; };   // row-major (P-1) x (P-1), by value
+
+// xs: `elems` elements of n doubles.  Axis of prime P: entries base + i mp stride, i < P - 1; one lane per column (j0 = 0 entry),
+// cols = elems * n / (P - 1) < 2^31.  s = 0.0; s = s + Lc[i][k] * col[k], k ascending, every operation rounded on its own.
+template <int P>
+__global__ void __launch_bounds__(256) k_gauss_axis(GaussChol C, double* xs, u32 n, u32 mp, u32 stride, u32 cols) {
+    constexpr int H = P - 1;
+    const u32 per = n / H;                                     // columns per element
+    for (u32 c = blockIdx.x * blockDim.x + threadIdx.x; c < cols; c += gridDim.x * blockDim.x) {
+        const u32 e = c / per, r = c - e * per;
+        const u32 lo = r % stride, t = r / stride, j1 = t % mp, hi = t / mp;
+        double* x = xs + (size_t)e * n + (size_t)hi * H * mp * stride + (size_t)j1 * stride + lo;
+        const size_t step = (size_t)mp * stride;
+        double col[H], out[H];
+#pragma unroll
+        for (int i = 0; i < H; ++i) col[i] = x[i * step];
+#pragma unroll
+        for (int i = 0; i < H; ++i) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k <= i; ++k) s = gauss::rn_add(s, gauss::rn_mul(C.l[i * H + k], col[k]));
+            out[i] = s;
+        }
+#pragma unroll
+        for (int i = 0; i < H; ++i) x[i * step] = out[i];
+    }
+}
+
+// xs: total = elems * n doubles (< 2^31).  dst: limb-major words of the first element, coset (nullable) as in k_gauss_sample.
+template <typename W>
+__global__ void __launch_bounds__(256) k_gauss_round(GaussPar G, const double* xs, W* dst, const u32* coset, u32 total) {
+    for (u32 idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
+        const int64_t z = gauss::round_coset(xs[idx], G.p, G.p ? coset[idx] : 0u);
+        const u32 e = idx / G.n, i = idx - e * G.n;
+        W* o = dst + ((size_t)e * G.L) * G.n + i;
+#pragma unroll
+        for (int j = 0; j < MAXL; ++j)
+            if ((u32)j < G.L) o[(size_t)j * G.n] = (W)gauss::reduce(z, G.q[j]);
+    }
+}
+
+// ---- SymmSHE encrypt, ring arithmetic ---------------------------------------------------------------------------------------
+// out[2b] = err[b] - c1 s, out[2b+1] = c1, c1 word (b, j, k) = splitmix64(seed + ((2 (ct0 + b) + 1) L + j) n + k) mod q_j: with
+// ct0 = 0 the words alch_buf_fill_uniform(out, seed) leaves in the odd elements.  words = batch * L * n.  VW words per access as in
+// k_ct_eval_sk.  The key element goes to Montgomery form on the way in (one product), read again by every ciphertext from L2.
+template <typename W, int VW>
+__global__ void k_ct_encrypt(DevRing<W> R, W* out, const W* err, const W* sk, size_t words, u64 seed, u64 ct0) {
+    typedef Pack<W, VW> P;
+    const u32 nv = R.n / VW;
+    const size_t ev = (size_t)R.L * nv;                      // packs per ring element
+    ALCH_WALK_INIT(nv, R.L);
+    ALCH_WALK(w, words / VW, wk) {
+        const ModP<W> m = R.mod[wk.mid];
+        const P s = reinterpret_cast<const P*>(sk)[(size_t)wk.mid * nv + wk.k];
+        const P e = reinterpret_cast<const P*>(err)[w];
+        const u64 pos = ((2 * (ct0 + (u64)wk.outer) + 1) * (u64)R.L + wk.mid) * (u64)R.n + (u64)wk.k * VW;
+        P c0, c1;
+#pragma unroll
+        for (int c = 0; c < VW; ++c) {
+            const W u = (W)(splitmix64(seed + pos + (u64)c) % (u64)m.q);
+            c1.v[c] = u;
+            c0.v[c] = sub_mod(e.v[c], mont_mul(u, mont_mul(s.v[c], m.r2, m), m), m.q);
+        }
+        const size_t o = w + wk.outer * ev;                  // component 0 of ciphertext wk.outer, same limb and position
+        reinterpret_cast<P*>(out)[o] = c0;
+        reinterpret_cast<P*>(out)[o + ev] = c1;
+    }
+}
+
+}  // namespace alch

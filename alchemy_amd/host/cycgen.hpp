@@ -32,6 +32,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <random>
@@ -41,6 +42,7 @@
 #include <vector>
 
 #include "../../include/alchemy_hip.h"
+#include "../csrc/gauss_sampler.hpp"
 
 namespace alchemy {
 namespace gen {
@@ -551,6 +553,27 @@ inline std::vector<int64_t> errorCosetDec(uint32_t m, double svar, int64_t p, co
         const int64_t c = centred(pt_dec[i], p);
         z[i] = c + p * (int64_t)std::llround((x[i] - (double)c) / (double)p);
     }
+    return z;
+}
+
+// ---- the counter-based sampler of the device encrypt path (alch_buf_gauss_dec) -----------------------------
+// The same definition as the device kernels, from the same header: element `elem` of the stream `seed`, the integers z on the decoding
+// basis.  p = 0: errorRounded; else errorCoset into coset + p R (coset: phi(m) residues in [0, p), p < 2^31), svar the caller's (encrypt
+// passes svar * p^2, as errorCosetDec does).  A statistical generator like the mt19937_64 above, and a different stream: the two
+// samplers agree in distribution, not in values.
+inline std::vector<int64_t> gaussDecCounter(uint32_t m, double svar, uint64_t seed, uint64_t elem, int64_t p = 0,
+                                            const std::vector<int64_t>* coset = nullptr) {
+    if (!alch::gauss::svar_ok(svar)) throw std::runtime_error("gaussDecCounter: svar must be finite and positive");
+    if (p < 0 || p >= ((int64_t)1 << 31) || (p != 0) != (coset != nullptr)) throw std::runtime_error("gaussDecCounter: bad coset");
+    const alch::gauss::Plan P = alch::gauss::make_plan(m, svar);
+    if (!alch::gauss::bound_ok(P, (uint32_t)p)) throw std::runtime_error("gaussDecCounter: svar too large");
+    std::vector<uint32_t> cw;
+    if (coset) {
+        if (coset->size() != P.n) throw std::runtime_error("gaussDecCounter: coset length");
+        for (int64_t v : *coset) cw.push_back((uint32_t)(((v % p) + p) % p));
+    }
+    std::vector<int64_t> z(P.n);
+    alch::gauss::element(P, seed, elem, (uint32_t)p, coset ? cw.data() : nullptr, z.data());
     return z;
 }
 

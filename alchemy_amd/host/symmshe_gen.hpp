@@ -437,6 +437,34 @@ inline bool decryptBatch(RingCache& rc, const SK& sk, const DevBatch& x, std::ve
     return true;
 }
 
+// SymmSHE encrypt of a resident plaintext batch (Pow basis, index pt.m | r.m()): the mirror image of decryptBatch.  embed / lInv on the
+// Z_p ring of the ciphertext index give the coset, alch_buf_gauss_dec draws errorCoset with svar * p^2 from the counter-based stream
+// splitmix64(seed), l / crt take it to the CRT basis and alch_ct_encrypt finishes with the uniform stream splitmix64(seed + 1).
+// Nothing crosses to the host but the key on its way in.  Another stream than `encrypt`'s mt19937_64: same distribution, other values.
+inline DevBatch encryptBatch(RingCache& rc, PtOps& ops, const Ring& r, const SK& sk, const PtBatch& pt, uint64_t seed) {
+    (void)ops;
+    if (pt.count == 0 || r.m() % pt.m) throw std::runtime_error("encryptBatch: a non-empty batch over an index dividing the ciphertext index");
+    const Ring& zp = rc.get(r.m(), {(uint64_t)pt.p}, false);
+    DevBatch out(r, pt.count);
+    out.enc = Encoding::LSD; out.k = 0; out.l = 1; out.p = pt.p; out.m = pt.m; out.basis = Basis::CRT;
+    const double svar = sk.svar * (double)pt.p * (double)pt.p;
+    uint64_t svar_bits;
+    memcpy(&svar_bits, &svar, sizeof svar_bits);
+    alch_buf *key = keyToDevice(r, sk), *big = nullptr, *err = nullptr;
+    auto release = [&]() { alch_buf_free(key); if (big) alch_buf_free(big); if (err) alch_buf_free(err); };
+    int rcl = alch_buf_alloc(zp.handle(), pt.count, &big);
+    if (rcl == ALCH_OK) rcl = alch_buf_alloc(r.handle(), pt.count, &err);
+    if (rcl == ALCH_OK) rcl = pt.m == r.m() ? alch_buf_copy(big, 0, pt.buf(), 0, pt.count) : alch_buf_embed(big, pt.buf(), pt.count, ALCH_BASIS_POW);
+    if (rcl == ALCH_OK) rcl = alch_buf_linv(big, 0, pt.count);
+    if (rcl == ALCH_OK) rcl = alch_buf_gauss_dec(err, 0, pt.count, svar_bits, big, 0, alch::gauss::mix64(seed), 0);
+    if (rcl == ALCH_OK) rcl = alch_buf_l(err, 0, pt.count);
+    if (rcl == ALCH_OK) rcl = alch_buf_crt(err, 0, pt.count);
+    if (rcl == ALCH_OK) rcl = alch_ct_encrypt(out.buf, pt.count, err, 0, key, 0, alch::gauss::mix64(seed + 1), 0);
+    release();
+    check(rcl, "encryptBatch");
+    return out;
+}
+
 // addPublic b on every ciphertext of the batch (LSD form)
 inline void addPublicBatch(PtOps& ops, DevBatch& x, const PtCyc& b) {
     x.toLSD();

@@ -13,7 +13,9 @@
 // max |c(s)| / q -- what the ERW interpreter logs (Crypto/Alchemy/Interpreter/ErrorRateWriter.hs:70-75, Eval.hs:151-160) -- is printed.
 //
 //   homomrlwr_replay [batch] [--seed N] [--dump DIR] [--per-element] [--per-element-resident] [--per-element-zip-host]
-//                    [--host-mode buffers|resident] [--var-scale F] [--quiet-stages] [--device-decrypt] [--device-plaintext]
+//                    [--host-mode buffers|resident] [--var-scale F] [--quiet-stages] [--device-decrypt] [--device-plaintext] [--device-encrypt]
+// --device-encrypt encrypts the RLWR secret through encryptBatch -- embed / lInv, alch_buf_gauss_dec, l / crt and alch_ct_encrypt on a
+// resident plaintext batch, the counter-based sampler seeded from --seed -- instead of the host-side encrypt; the closing check is unchanged.
 // --device-plaintext computes the plaintext side (eval ringRound (s * a)) on resident batches -- PtBatch over alch_pt_mul, alch_pt_eval_lin,
 // alch_pt_rescale and alch_buf_add_bcast, one call per operation for all inputs -- instead of one ring element at a time; same lines, same PASS.
 // --device-decrypt runs the closing check (decrypt and error rate of every result) through decryptBatch -- one alch_ct_decrypt_lift
@@ -60,7 +62,7 @@ int main(int argc, char** argv) {
     size_t B = 4;
     uint64_t seed = 2026;
     std::string dump;
-    bool per_element = false, per_resident = false, per_ziphost = false, quiet = false, device_decrypt = false, device_plaintext = false;
+    bool per_element = false, per_resident = false, per_ziphost = false, quiet = false, device_decrypt = false, device_plaintext = false, device_encrypt = false;
     double var_scale = 1.0;
     Mode host_mode = Mode::Resident;
     for (int i = 1; i < argc; ++i) {
@@ -72,6 +74,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--quiet-stages")) quiet = true;
         else if (!strcmp(argv[i], "--device-decrypt")) device_decrypt = true;
         else if (!strcmp(argv[i], "--device-plaintext")) device_plaintext = true;
+        else if (!strcmp(argv[i], "--device-encrypt")) device_encrypt = true;
         else if (!strcmp(argv[i], "--var-scale") && i + 1 < argc) var_scale = atof(argv[++i]);
         else if (!strcmp(argv[i], "--host-mode") && i + 1 < argc) host_mode = !strcmp(argv[++i], "buffers") ? Mode::HostBuffers : Mode::Resident;
         else B = (size_t)atoi(argv[i]);
@@ -115,7 +118,8 @@ int main(int argc, char** argv) {
         auto randPt = [&](uint32_t m) { PtCyc x{m, P, Basis::Pow, std::vector<int64_t>(totient(m))}; for (auto& v : x.v) v = (int64_t)(rng() % (uint64_t)P); return x; };
         const PtCyc s = randPt(H[0]);
         const Ring& r0 = rc.get(HP[0], moduli(tuns[0].lin));
-        const CT enc_s = encrypt(rc, ops, r0, sk[0], s, rng);
+        const CT enc_s = device_encrypt ? encryptBatch(rc, ops, r0, sk[0], ops.upload(std::vector<PtCyc>(1, s)), seed).download(0)
+                                        : encrypt(rc, ops, r0, sk[0], s, rng);
         printf("Generating function... %.2f s (6 keys, 5 linear functions with tunnel hints, 4 quadratic hints, enc(s))\n", now() - t0);
 
         std::vector<PtCyc> as;

@@ -149,3 +149,9 @@ foreign import ccall safe   "alch_pt_linear_free"      c_ptLinearFree    :: Ptr 
 foreign import ccall safe   "alch_pt_eval_lin"         c_ptEvalLin       :: Ptr () -> Ptr AlchBuf -> Ptr AlchBuf -> CSize -> CUInt -> IO CInt
 foreign import ccall safe   "alch_pt_rescale"          c_ptRescale       :: Ptr AlchBuf -> Ptr AlchBuf -> CSize -> IO CInt
 foreign import ccall safe   "alch_buf_add_bcast"       c_bufAddBcast     :: Ptr AlchBuf -> Ptr AlchBuf -> Ptr AlchBuf -> CSize -> CSize -> IO CInt
+-- encrypt on resident batches (added within library version 1.8): the counter-based Gaussian on the decoding basis (doubles cross as
+-- their IEEE bit patterns) and SymmSHE encrypt's ring arithmetic; the first two are host-only
+foreign import ccall safe   "alch_gauss_table"         c_gaussTable      :: Ptr Word64 -> Ptr CSize -> IO CInt
+foreign import ccall safe   "alch_gauss_plan"          c_gaussPlan       :: Word32 -> Word64 -> Ptr Word64 -> Ptr Word64 -> Ptr CSize -> IO CInt
+foreign import ccall safe   "alch_buf_gauss_dec"       c_bufGaussDec     :: Ptr AlchBuf -> CSize -> CSize -> Word64 -> Ptr AlchBuf -> CSize -> Word64 -> Word64 -> IO CInt
+foreign import ccall safe   "alch_ct_encrypt"          c_ctEncrypt       :: Ptr AlchBuf -> CSize -> Ptr AlchBuf -> CSize -> Ptr AlchBuf -> CSize -> Word64 -> Word64 -> IO CInt

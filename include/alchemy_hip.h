@@ -557,6 +557,46 @@ int alch_pt_rescale(const alch_buf *src_zp, alch_buf *dst_zp, size_t count);
  * three buffers; dst may be src.  The x * (1 + x) of the rescale tree uses it. */
 int alch_buf_add_bcast(alch_buf *dst, const alch_buf *src, const alch_buf *one, size_t index, size_t count);
 
+/* ---- encrypt on resident batches (added within 1.8; probe for the symbols) ------------------------------------------------------
+ * SymmSHE encrypt (PT2CT.hs:84-87): an error term from the coset pt + p R on the decoding basis, a uniform c1, c0 = err - c1 s.  The
+ * mirror image of alch_ct_decrypt_lift.  The error sampler is COUNTER-BASED: every stored word is an integer-exact function of
+ * (seed, position), so a batch cut into chunks, the host mirror (alchemy_amd/host/cycgen.hpp: gaussDecCounter) and the Python model
+ * of the tests give the same words.  Definition (arithmetic on seeds and counters mod 2^64):
+ *   table      T[t] = floor(2^63 P(|K| <= t)), K ~ D_{Z,64}; 582 entries, the last one 2^63 - 1 (alch_gauss_table)
+ *   deviate    coefficient i of element e, n = phi(m): c = (elem0 + e) n + i; w0 = splitmix64(seed + 2c), w1 = splitmix64(seed + 2c + 1);
+ *              t = #{ j : T[j] <= w0 >> 1 }; k = (w0 & 1) ? -t : t; f = k 2^32 + (w1 >> 32) - 2^31; x = (double)f * scale
+ *   scale      sigma / (sqrt(4096 + 1/12) * 2^32), sigma = sqrt(svar * (m / rad m) / (2 pi)) (alch_gauss_plan)
+ *   correlate  for every odd prime p of m, ascending, the lower Cholesky factor of p I - J along the axis (the loop of tGaussianDec in
+ *              cycgen.hpp), s = 0.0; s = s + Lc[i][k] * col[k] for k = 0 .. i, every product and every sum rounded on its own
+ *   round      R(x) = sign(x) floor(|x| + 0.5); errorRounded: z = R(x); errorCoset with coset word v mod p: c = v centred,
+ *              z = c + p R((x - c) / p); the stored word of limb j is z mod q_j, on the DECODING basis
+ * splitmix64 is a STATISTICAL generator, not a cryptographic one -- like the mt19937_64 of the host path it stands beside.
+ * Doubles cross the ABI as their IEEE-754 bit patterns in uint64_t. */
+/* Host only (no device needed).  cdt = NULL: *len = the table's length; else *len >= that on entry, the table is copied. */
+int alch_gauss_table(uint64_t *cdt, size_t *len);
+/* Host only.  scale (nullable) and the Cholesky factors of the ODD primes of m, ascending, each row-major and full (p-1) x (p-1) with
+ * zeros above the diagonal.  chol_bits = NULL: *chol_len = their total length; else *chol_len >= that on entry.
+ * ALCH_E_INVALID: m < 1; svar not finite or <= 0. */
+int alch_gauss_plan(uint32_t m, uint64_t svar_bits, uint64_t *scale_bits, uint64_t *chol_bits, size_t *chol_len);
+/* dst[first + e], e < count: errorRounded (coset_zp = NULL) or errorCoset of scaled variance svar (the caller's: encrypt passes
+ * svar * p^2) on the decoding basis, reduced into every modulus of dst's ring -- any ring of alch_ring_create or
+ * alch_ring_create_nocrt (modulus 0, the integers: z itself).  coset_zp: a buffer of a ONE-modulus ring of the same index, modulus
+ * 2 <= p < 2^31; element coset_first + e is the coset of element e.  elem0 only shifts the counters: calls over consecutive chunks
+ * with elem0 advanced give the words of one call.  Work is queued on dst's ring; a coset ring on another stream is ordered before and
+ * after it.  count = 0: ALCH_OK, nothing queued.  ALCH_E_INVALID: svar not finite or <= 0, or so large that |z| < 2^62 cannot be
+ * guaranteed (from scale, the table length and the row sums of the Cholesky factors); index, modulus-count or device mismatch of the
+ * coset ring; a range outside a buffer; overlapping ranges other than coset == destination.  ALCH_E_UNSUPPORTED: an odd prime of
+ * the index above 13. */
+int alch_buf_gauss_dec(alch_buf *dst, size_t first, size_t count, uint64_t svar_bits, const alch_buf *coset_zp, size_t coset_first,
+                       uint64_t seed, uint64_t elem0);
+/* out[2b] = err_crt[err_first + b] - c1 * sk_crt[sk_index], out[2b + 1] = c1, b < batch: `CT LSD 0 1 [c0, c1]`, everything on the CRT
+ * basis of one ring.  Word (b, limb j, slot k) of c1 is splitmix64(seed + ((2 (ct0 + b) + 1) L + j) n + k) mod q_j: with ct0 = 0 the
+ * words alch_buf_fill_uniform(out, seed) puts into the odd elements; ct0 shifts the ciphertext counter as elem0 does above.
+ * batch = 0: ALCH_OK, nothing queued.  ALCH_E_INVALID: null buffer; buffers of different rings; out smaller than 2 * batch; a range or
+ * the key index outside its buffer; out overlapping err_crt's range or the key.  ALCH_E_NO_CRT: a ring without CRT basis. */
+int alch_ct_encrypt(alch_buf *out, size_t batch, const alch_buf *err_crt, size_t err_first, const alch_buf *sk_crt, size_t sk_index,
+                    uint64_t seed, uint64_t ct0);
+
 /* ---- modSwitch building block (Eval.hs:130) ---------------------------------------
  * Rescale (a,b) -> b on Pow-basis elements: src lives in ring_src (L limbs), dst in ring_dst whose
  * limbs are ring_src's limbs 1..L-1:  dst_j = q_0^-1 * (src_j - reduce(lift src_0)). */
