@@ -804,8 +804,7 @@ __global__ void __launch_bounds__(256) k_tunnel_mac_e(DevRing<u32> R, u32* out, 
         const u32 limb = wk.mid;
         const W q = R.mod[limb].q, qni = R.mod[limb].qni;
         const u32 se = slot_e ? slot_e[(size_t)wk.k * VL] : wk.k * (u32)VL;      // no slot table: the digits were transformed in S' itself
-        const u32 kmax = 0xFFFFFFFFu / q;                       // (K + 2) q < 2^32
-        const u32 K = kmax >= 4 ? (kmax - 2 > 8 ? 8u : kmax - 2) : 0u;
+        const u32 K = lazy_group(q);                            // (K + 2) q < 2^32
         const bool lazy = K >= 2;
         const W r1 = lazy ? R.mod[limb].r1 : (W)1;            // not lazy: the accumulators hold the running sum itself, in [0, q)
         u64 a0[TILE][VL], a1[TILE][VL];
@@ -839,7 +838,7 @@ __global__ void __launch_bounds__(256) k_tunnel_mac_e(DevRing<u32> R, u32* out, 
             }
         }
         const size_t dstep = (size_t)R.L * n_d;
-        auto redc = [&](u64 t) -> W { const W m = (W)t * qni; return (W)((t + (u64)m * q) >> 32); };     // t < q 2^32 -> [0, 2q)
+        auto redc = [&](u64 t) -> W { return mont_red_lazy(t, q, qni); };     // t < q 2^32 -> [0, 2q)
         if (lazy) {
             for (u32 d0 = 0; d0 < D; d0 += K) {
                 const u32 dend = d0 + K < D ? d0 + K : D;
@@ -1177,8 +1176,7 @@ __global__ void __launch_bounds__(256) k_tun2_mac(DevRing<W> R, W* out, const W*
         bool lazy = false;
         u32 K = 0;
         if constexpr (sizeof(W) == 4) {
-            const u32 kmax = 0xFFFFFFFFu / (u32)q;                 // (K + 2) q < 2^32
-            K = kmax >= 4 ? (kmax - 2 > 8 ? 8u : kmax - 2) : 0u;
+            K = lazy_group((u32)q);                                // (K + 2) q < 2^32
             lazy = K >= 2;
         }
         const u64 r1 = lazy ? (u64)m.r1 : 1;                       // not lazy: the accumulators hold the running sum itself, in [0, q)
@@ -1207,7 +1205,7 @@ __global__ void __launch_bounds__(256) k_tun2_mac(DevRing<W> R, W* out, const W*
         const size_t dstep = (size_t)R.L * n_d;
         if (lazy) {
             if constexpr (sizeof(W) == 4) {
-                auto redc = [&](u64 t) -> u32 { const u32 mm = (u32)t * qni; return (u32)((t + (u64)mm * q) >> 32); };     // t < q 2^32 -> [0, 2q)
+                auto redc = [&](u64 t) -> u32 { return mont_red_lazy(t, (u32)q, (u32)qni); };     // t < q 2^32 -> [0, 2q)
                 for (u32 d0 = 0; d0 < D; d0 += K) {
                     const u32 dend = d0 + K < D ? d0 + K : D;
                     for (u32 d = d0; d < dend; ++d) {
@@ -1384,12 +1382,8 @@ static int build_gen_ring(alch_ring* r, DevRing<W>& d, GenDev<W>& g) {
     for (int i = 0; i < h.npass; ++i) g.pass[i] = h.pass[i];
     for (int i = 0; i < h.nfact; ++i) g.fact[i] = h.fact[i];
     g.plain = (!r->has_crt && !r->zdom) ? 1 : 0;
-    g.smallq = r->has_crt ? 1 : 0;
-    for (int j = 0; j < L; ++j) if (r->q[j] >= 1753413056ull) g.smallq = 0;      // 6 q^2 < 2^64
-    if (g.smallq) {                                                                // 6 q < 2^32: examples/Tunnel.hs's moduli
-        g.smallq = 2;
-        for (int j = 0; j < L; ++j) if (r->q[j] >= 715827882ull) g.smallq = 1;
-    }
+    g.smallq = (r->has_crt && sizeof(W) == 4) ? 2 : 0;                            // the least level over the limbs (dense_level)
+    for (int j = 0; j < L && g.smallq; ++j) g.smallq = std::min(g.smallq, dense_level(r->q[j]));
     u64 maxhalf = 0;
     for (int j = 0; j < L; ++j) maxhalf = std::max(maxhalf, r->q[j] ? (r->q[j] - 1) / 2 : 0);
     if (!r->has_crt) {

@@ -115,43 +115,7 @@ hipError_t gen_ks_dispatch(const DevRing<u64>& R, const GenDev<u64>& G, const Ge
 // ------------------------------------------------------------------------------------------------------
 // passes
 // ------------------------------------------------------------------------------------------------------
-// sum_t x[t] * M[t] (Montgomery: M holds M R) for canonical x, M < q < 2^31.
-// 32-bit words: four products are summed in 64 bits before one reduction -- 4 q^2 < 2^64, the sum's high word is < 2q, one
-// conditional subtraction brings the sum below q 2^32, then a single Montgomery reduction: 10 instructions per four terms
-// instead of 20.  64-bit words: one product at a time.
-// LVL 1 (every modulus of the ring below 2^32 / sqrt(6) = 1 753 413 056: all of the reference's): up to SIX products are summed
-// before one reduction -- 6 q^2 < 2^64, the sum's high word is < 2.2 q and takes two conditional subtractions (2q, q).  One
-// Montgomery reduction per row of a CRT_13 / DFT_13 half-matrix instead of two: 14 instructions per row instead of 21.
-// LVL 2 (every modulus below 2^32 / 6 = 715 827 882: all of examples/Tunnel.hs's): six q^2 stay below q 2^32, the sum's high word is
-// already below q -- no conditional subtraction in front of the reduction (10 instructions per six-term row instead of 14).  Any level:
-// a chunk of one or two products needs none either (2 q^2 < q 2^32 for every q < 2^31).
-template <int R, int LVL = 0, typename MP>
-__device__ __forceinline__ u32 dense_row(const u32* x, MP M, u32 q, u32 qni) {
-    constexpr int CH = LVL ? 6 : 4;
-    u32 acc = 0;
-#pragma unroll
-    for (int t0 = 0; t0 < R; t0 += CH) {
-        const int terms = (R - t0 < CH) ? R - t0 : CH;
-        u64 p = (u64)x[t0] * M[t0];
-#pragma unroll
-        for (int t = t0 + 1; t < t0 + CH && t < R; ++t) p += (u64)x[t] * M[t];
-        u32 hi = (u32)(p >> 32);
-        if (LVL == 1 && terms > 4) hi = csub(hi, 2u * q);                       // more than four terms: high word < 2.2 q
-        if (terms > 2 && LVL != 2) hi = csub(hi, q);                             // high word < 2q -> < q
-        const u64 pr = ((u64)hi << 32) | (u32)p;
-        const u32 m = (u32)pr * qni;
-        const u32 v = csub((u32)((pr + (u64)m * q) >> 32), q);
-        acc = t0 ? csub(acc + v, q) : v;
-    }
-    return acc;
-}
-template <int R, int LVL = 0, typename MP>
-__device__ __forceinline__ u64 dense_row(const u64* x, MP M, u64 q, u64 qni) {
-    u64 acc = csub(mont_mul_lazy(x[0], M[0], q, qni), q);
-#pragma unroll
-    for (int t = 1; t < R; ++t) acc = csub(acc + csub(mont_mul_lazy(x[t], M[t], q, qni), q), q);
-    return acc;
-}
+// dense_row (the lazy row sums of the CRT_p / DFT_p passes) lives in modarith.hpp, where a host program can call it.
 template <typename W> __device__ __forceinline__ W gadd(W a, W b, W q) { return csub((W)(a + b), q); }
 // a - b mod q for canonical a, b: the difference wraps to a huge word exactly when a < b, and then adding q wraps back below it
 template <typename W> __device__ __forceinline__ W gsub(W a, W b, W q) { const W d = a - b, e = d + q; return e < d ? e : d; }

@@ -85,13 +85,12 @@ __global__ void k_pt_mac(DevRing<W> R, W* out, const W* x, const W* y, size_t co
         bool done = false;
         if constexpr (sizeof(W) == 4) {
             const u32 q = (u32)m.q, qni = (u32)m.qni, r1 = (u32)m.r1;
-            const u32 kmax = 0xFFFFFFFFu / q;
-            const u32 K = kmax >= 4 ? (kmax - 2 > 8 ? 8u : kmax - 2) : 0u;
+            const u32 K = lazy_group(q);
             if (K >= 2) {
                 u64 acc[VW];
 #pragma unroll
                 for (int c = 0; c < VW; ++c) acc[c] = 0;
-                auto redc = [&](u64 t) -> u32 { const u32 f = (u32)t * qni; return (u32)((t + (u64)f * q) >> 32); };   // t < q 2^32 -> [0, 2q)
+                auto redc = [&](u64 t) -> u32 { return mont_red_lazy(t, q, qni); };   // t < q 2^32 -> [0, 2q)
                 for (u32 i0 = 0; i0 < d_rel; i0 += K) {
                     const u32 iend = i0 + K < d_rel ? i0 + K : d_rel;
                     for (u32 i = i0; i < iend; ++i) {

@@ -103,6 +103,19 @@ ALCH_HD u32 mont_red_lazy(u64 p, u32 q, u32 qni) {
     return (u32)((p + (u64)m * q) >> 32);
 }
 
+// Lazy inner products on 32-bit words: how many products x y (x, y < q) one 64-bit accumulator takes between two Montgomery
+// reductions.  With t in [0, 2q) the running sum carried as t (R mod q) < 2 q^2, a group of K products keeps
+//   acc = t (R mod q) + sum_K x y < (K + 2) q^2 < q 2^32   as long as   (K + 2) q < 2^32,
+// the bound of mont_red_lazy.  K = floor((2^32 - 1) / q) - 2, at most 8; 0 (one Montgomery product at a time) where a group of
+// two does not fit.
+ALCH_HD u32 lazy_group(u32 q) {
+    const u32 kmax = 0xFFFFFFFFu / q;                       // (K + 2) q < 2^32
+    return kmax >= 4 ? (kmax - 2 > 8 ? 8u : kmax - 2) : 0u;
+}
+
+// The variant of dense_row a modulus allows: 2 below 2^32 / 6 (6 q < 2^32), 1 below 2^32 / sqrt(6) (6 q^2 < 2^64), else 0.
+ALCH_HD int dense_level(u64 q) { return q < 715827882ull ? 2 : q < 1753413056ull ? 1 : 0; }
+
 // c in [0,q) -> its centred representative in [-(q-1)/2, (q-1)/2]; negate: that of -c.
 ALCH_HD int32_t centre_const(u32 c, u32 q, bool negate) {
     const int32_t s = c > ((q - 1) >> 1) ? (int32_t)c - (int32_t)q : (int32_t)c;
@@ -202,6 +215,44 @@ ALCH_HD void bfly_inv(u64& x, u64& y, Sh64 w, u64 q, u64 /*qni*/) {
 // every other twiddle type: the stage position does not matter
 template <typename W, typename TW>
 ALCH_HD void bfly_fwd_st(W& x, W& y, TW w, W q, W qni, bool, bool) { bfly_fwd(x, y, w, q, qni); }
+
+// sum_t x[t] * M[t] (Montgomery: M holds M R) for canonical x, M < q < 2^31.
+// 32-bit words: four products are summed in 64 bits before one reduction -- 4 q^2 < 2^64, the sum's high word is < 2q, one
+// conditional subtraction brings the sum below q 2^32, then a single Montgomery reduction: 10 instructions per four terms
+// instead of 20.  64-bit words: one product at a time.
+// LVL 1 (every modulus of the ring below 2^32 / sqrt(6) = 1 753 413 056: all of the reference's): up to SIX products are summed
+// before one reduction -- 6 q^2 < 2^64, the sum's high word is < 2.2 q and takes two conditional subtractions (2q, q).  One
+// Montgomery reduction per row of a CRT_13 / DFT_13 half-matrix instead of two: 14 instructions per row instead of 21.
+// LVL 2 (every modulus below 2^32 / 6 = 715 827 882: all of examples/Tunnel.hs's): six q^2 stay below q 2^32, the sum's high word is
+// already below q -- no conditional subtraction in front of the reduction (10 instructions per six-term row instead of 14).  Any level:
+// a chunk of one or two products needs none either (2 q^2 < q 2^32 for every q < 2^31).
+template <int R, int LVL = 0, typename MP>
+ALCH_HD u32 dense_row(const u32* x, MP M, u32 q, u32 qni) {
+    constexpr int CH = LVL ? 6 : 4;
+    u32 acc = 0;
+#pragma unroll
+    for (int t0 = 0; t0 < R; t0 += CH) {
+        const int terms = (R - t0 < CH) ? R - t0 : CH;
+        u64 p = (u64)x[t0] * M[t0];
+#pragma unroll
+        for (int t = t0 + 1; t < t0 + CH && t < R; ++t) p += (u64)x[t] * M[t];
+        u32 hi = (u32)(p >> 32);
+        if (LVL == 1 && terms > 4) hi = csub(hi, 2u * q);                       // more than four terms: high word < 2.2 q
+        if (terms > 2 && LVL != 2) hi = csub(hi, q);                             // high word < 2q -> < q
+        const u64 pr = ((u64)hi << 32) | (u32)p;
+        const u32 m = (u32)pr * qni;
+        const u32 v = csub((u32)((pr + (u64)m * q) >> 32), q);
+        acc = t0 ? csub(acc + v, q) : v;
+    }
+    return acc;
+}
+template <int R, int LVL = 0, typename MP>
+ALCH_HD u64 dense_row(const u64* x, MP M, u64 q, u64 qni) {
+    u64 acc = csub(mont_mul_lazy(x[0], M[0], q, qni), q);
+#pragma unroll
+    for (int t = 1; t < R; ++t) acc = csub(acc + csub(mont_mul_lazy(x[t], M[t], q, qni), q), q);
+    return acc;
+}
 
 // ---- host-side helpers (table building) ------------------------------------------------------
 inline u64 h_mulmod(u64 a, u64 b, u64 q) { return (u64)(((unsigned __int128)a * b) % q); }

@@ -276,3 +276,88 @@ def oracle_tunnel(oracle_lib, r_p, s_p, qs, lin_crt, ks_crt, c0, c1, s_pre=None,
             acc0 = Os.add(acc0, Os.mul(dc, ks_crt[(i * len(digs) + t) * 2]))
             acc1 = Os.add(acc1, Os.mul(dc, ks_crt[(i * len(digs) + t) * 2 + 1]))
     return (Os.crtinv(acc0), Os.crtinv(acc1)) if pow_out else (acc0, acc1)
+
+
+# ---- 32-bit words: the moduli at which a lazy 64-bit sum changes its group size ------------------------------------------------------
+DENSE_LEVEL2_BELOW = 715827882                  # 2^32 / 6: below it six products stay under q 2^32 (dense_row level 2)
+DENSE_LEVEL1_BELOW = 1753413056                 # 2^32 / sqrt(6): below it six products stay under 2^64 (level 1)
+
+
+def lazy_group(q):
+    """Products per 64-bit group of the 32-bit inner-product kernels (k_tunnel_mac_e, k_tun2_mac, k_pt_mac), from the documented
+    bound alone: the largest K <= 8 with (K + 2) q < 2^32, and 0 (one product at a time) where not even two fit."""
+    k = min(8, ((1 << 32) - 1) // q - 2)
+    assert k < 2 or (k + 2) * q < (1 << 32) and (k == 8 or (k + 3) * q >= (1 << 32))
+    return k if k >= 2 else 0
+
+
+def group_class_primes(m, kmax):
+    """(top, bottom): the largest and the smallest prime q = 1 (mod m) with (2^32 - 1) // q == kmax.  The top of a class has the
+    least headroom under (K + 2) q < 2^32; the bottom is the first modulus that gets one product more."""
+    top = primes_below(m, 1, ((1 << 32) - 1) // kmax + 1)[0]
+    bottom = primes_1_mod(m, 1, ((1 << 32) - 1) // (kmax + 1))[0]
+    assert ((1 << 32) - 1) // top == kmax == ((1 << 32) - 1) // bottom, (m, kmax, top, bottom)
+    return top, bottom
+
+
+def level_edge_primes(m):
+    """Primes q = 1 (mod m) next to the constants that choose the variant of dense_row (general-index CRT_p / DFT_p passes):
+    'below2' / 'above2': the two largest below 2^32 / 6 (largest first) and the two smallest at or above it; 'below1' / 'above1':
+    the same at 2^32 / sqrt(6); 'top': the two largest below 2^31."""
+    return {"below2": primes_below(m, 2, DENSE_LEVEL2_BELOW), "above2": primes_1_mod(m, 2, DENSE_LEVEL2_BELOW - 1),
+            "below1": primes_below(m, 2, DENSE_LEVEL1_BELOW), "above1": primes_1_mod(m, 2, DENSE_LEVEL1_BELOW - 1),
+            "top": primes_below(m, 2, 1 << 31)}
+
+
+def dense_level(qs):
+    """The dense_row variant a 32-bit general-index ring with these moduli runs: the least level over its limbs."""
+    return min(2 if q < DENSE_LEVEL2_BELOW else 1 if q < DENSE_LEVEL1_BELOW else 0 for q in qs)
+
+
+def threshold_moduli(rng, m, count):
+    """`count` distinct primes = 1 (mod m) below 2^31 from both ends of every group-size class and from the level edges: the modulus
+    draw of the sweeps (rng: random.Random)."""
+    pool = {q for kmax in range(2, 12) for q in group_class_primes(m, kmax)} | {q for v in level_edge_primes(m).values() for q in v}
+    return rng.sample(sorted(q for q in pool if q < (1 << 31)), count)
+
+
+def tunnel_worst_operands(oracle_lib, rp, sp, qs, batch, plus, check_digits):
+    """The worst case of a tunnel's hint inner product on 32-bit words, as operands(rng, d_rel, D, n_r, n_s) -> (lin, ks, cts) (D: digits
+    per E'-coefficient; the kernel sums d_rel D products per slot).  lin, c0 and the odd ciphertexts: extreme words.  Hint rows:
+    extreme words in the upper half of the slots, q-1 in the lower half.  c1 of the even ciphertexts: crt of the element whose every
+    E'-coefficient is the constant -1 (+1 with plus: s_pre = -1 turns it round) -- the Pow-basis word at position rows[i][0] of
+    every row of coeffs_indices, zero elsewhere.  Every TrivGad digit of it is then the constant -1, whose CRT image is q-1 in every
+    slot: with the lower half of the hint the kernel sums D products (q-1)^2.  check_digits: assert exactly that with the oracle,
+    following oracle_tunnel's own steps."""
+    import math
+    from oracle import model_gen as G
+    e_p = math.gcd(rp, sp)
+    ie, ir, isx = G.Index(e_p), G.Index(rp), G.Index(sp)
+    rows, emb = np.array(G.coeffs_indices(ie, ir)), np.array(G.embed_indices(ie, isx))
+    L = len(qs)
+    qv = np.array(qs, dtype=np.int64)
+
+    def make(rng, d_rel, D, n_r, n_s):
+        assert (n_r, n_s) == (ir.n, isx.n) and rows.shape == (d_rel, ie.n)
+        Or, Os = oracle_lib.GenRing(rp, qs), oracle_lib.GenRing(sp, qs)
+        lin, ks = extreme_words(rng, d_rel, n_s, qs), extreme_words(rng, 2 * d_rel * D, n_s, qs)
+        ks[:, :n_s // 2, :] = qv - 1
+        cts = extreme_words(rng, 2 * batch, n_r, qs)
+        x = np.zeros((n_r, L), dtype=np.int64)
+        x[rows[:, 0], :] = 1 if plus else qv - 1
+        worst = Or.crt(x)
+        for ct in range(0, batch, 2):
+            cts[2 * ct + 1] = worst
+        if check_digits:
+            assert D == L                                         # TrivGad: one digit per limb and E'-coefficient
+            c1p = Or.scale(Or.crtinv(worst), [q - 1 for q in qs] if plus else [1] * L)
+            for row in rows:
+                x1 = np.zeros((n_s, L), dtype=np.int64)
+                x1[emb] = c1p[row]
+                digs = Os.decompose_triv(x1)
+                assert len(digs) == L
+                for d in digs:
+                    assert np.array_equal(Os.crt(d), np.broadcast_to(qv - 1, (n_s, L))), "a digit's CRT image is not q-1 everywhere"
+        return lin, ks, cts
+
+    return make

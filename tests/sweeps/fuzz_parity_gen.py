@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Randomised parity sweep on general cyclotomic indices: alch_ct_mul_relin (TrivGad), alch_ct_mul_full (TrivGad) and alch_ct_mod_switch
-on random indices m = 2^a 3^b 5^c 7^d 13^e with phi(m) <= 3000, random 1..5 moduli = 1 mod m (29..31 bits), random batches and launch
+on random indices m = 2^a 3^b 5^c 7^d 13^e with phi(m) <= 3000, random 1..5 moduli = 1 mod m (29..31 bits, or next to
+the constants that choose dense_row's variant and the ends of the group-size classes: helpers.threshold_moduli), random batches and launch
 options (gen_fused, gen_nt, rs_lin), every result word compared with the general C restatement.  usage: tests/sweeps/fuzz_parity_gen.py [seconds] [seed]"""
 import os, random, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -9,7 +10,7 @@ import numpy as np
 import alchemy_amd as A
 from alchemy_amd import capi
 from oracle import cref
-from helpers import oracle_full_mul_general, primes_1_mod
+from helpers import oracle_full_mul_general, primes_1_mod, threshold_moduli
 
 OPTS = {"gen_fused": [0, 1], "gen_nt": [0, 128, 256, 512], "rs_lin": [0, 1], "scratch_mib": [1, 64]}
 
@@ -38,7 +39,8 @@ def main():
         if n < 4 or n > 3000 or m & (m - 1) == 0: continue           # two-power indices have their own sweep
         if n < 200 and rng.random() < 0.85: continue                 # mostly rings of a few hundred to 3000 coefficients
         L = rng.randint(1, 5)
-        qs = primes_1_mod(m, L, lo=rng.choice([1 << 28, 1 << 29, (1 << 30) + (1 << 29), 715_000_000]))
+        if rng.random() < 0.33: qs = threshold_moduli(rng, m, L)
+        else: qs = primes_1_mod(m, L, lo=rng.choice([1 << 28, 1 << 29, (1 << 30) + (1 << 29), 715_000_000]))
         if max(qs) >= 1 << 31: continue
         rng.shuffle(qs)
         batch = rng.randint(1, 9)

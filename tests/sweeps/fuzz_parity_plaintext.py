@@ -17,7 +17,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import alchemy_amd as A                      # noqa: E402
-from helpers import primes_1_mod             # noqa: E402
+from helpers import primes_1_mod, threshold_moduli   # noqa: E402
 from oracle import model_gen as G            # noqa: E402
 
 INDICES = [4, 8, 9, 12, 15, 16, 20, 21, 28, 32, 36, 45, 63, 64, 91, 128, 448]
@@ -25,9 +25,9 @@ MODULI = [2, 4, 7, 8, 9, 32, 100]
 
 
 def lift_ring(m, rng):
-    kind = rng.choice(["two31", "one60", "three29"])
+    kind = rng.choice(["two31", "one60", "three29", "edges", "edges"])   # edges: the ends of k_pt_mac's group-size classes
     qs = {"two31": lambda: primes_1_mod(m, 2, 1 << 30), "one60": lambda: primes_1_mod(m, 1, 1 << 59),
-          "three29": lambda: primes_1_mod(m, 3, 1 << 28)}[kind]()
+          "three29": lambda: primes_1_mod(m, 3, 1 << 28), "edges": lambda: threshold_moduli(rng, m, 2)}[kind]()
     r = A.Ring(m, qs)
     r.set_option("scratch_mib", rng.choice([1, 2, 4096]))
     return r, kind

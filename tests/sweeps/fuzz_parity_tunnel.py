@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Randomised parity sweep of alch_ct_tunnel: random index pairs (r', s') with lcm <= 60000 and phi <= 3000 that satisfy Lol's tunnel
-conditions (alch_tunnel_info decides), 1..4 moduli = 1 mod lcm(r', s'), TrivGad or BaseBGad 2 hints, random linear functions, hints,
-ciphertexts, encoding scalars, tunnel_ep / tunnel_fused options and the Pow-basis-out flag, against the C restatement's composition
+conditions (alch_tunnel_info decides), 1..4 moduli = 1 mod lcm(r', s') (one case in three: from the ends of the group-size classes
+of the lazy inner product and the level edges of dense_row, helpers.threshold_moduli), TrivGad or BaseBGad 2 hints, random linear functions, hints,
+ciphertexts (one TrivGad case in four: the worst case of the inner product, helpers.tunnel_worst_operands), encoding scalars, tunnel_ep / tunnel_fused options and the Pow-basis-out flag, against the C restatement's composition
 (tests/helpers.py::oracle_tunnel -- the checker of the tunnel tests).  usage: tests/sweeps/fuzz_parity_tunnel.py [seconds] [seed]"""
 import math, os, random, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -10,7 +11,7 @@ import numpy as np
 import alchemy_amd as A
 from alchemy_amd import capi
 from oracle import cref
-from helpers import oracle_tunnel, primes_1_mod
+from helpers import oracle_tunnel, primes_1_mod, threshold_moduli, tunnel_worst_operands
 
 
 def phi(m):
@@ -42,7 +43,8 @@ def main():
         if lcm > 60000 or max(phi(rp), phi(sp)) > 3000 or min(phi(rp), phi(sp)) < 4: continue
         if (rp & (rp - 1)) == 0 and (sp & (sp - 1)) == 0: continue
         L = rng.randint(1, 4)
-        qs = primes_1_mod(lcm, L, lo=rng.choice([1 << 28, 1 << 29, 1 << 30]))
+        edges = rng.random() < 0.33
+        qs = threshold_moduli(rng, lcm, L) if edges else primes_1_mod(lcm, L, lo=rng.choice([1 << 28, 1 << 29, 1 << 30]))
         if max(qs) >= 1 << 31: continue
         try:
             gr, gs = A.Ring(rp, qs), A.Ring(sp, qs)
@@ -57,6 +59,10 @@ def main():
         rnd = lambda c, n: np.stack([np.stack([nprng.integers(0, q, size=n, dtype=np.int64) for q in qs], axis=1) for _ in range(c)])
         lin, ks, cts = rnd(d_rel, gs.n), rnd(2 * d_rel * D, gs.n), rnd(2 * batch, gr.n)
         s_pre = None if rng.random() < 0.5 else [rng.randrange(1, q) for q in qs]
+        worst = gadget == "triv" and rng.random() < 0.25
+        if worst:
+            s_pre = rng.choice([None, [q - 1 for q in qs]])
+            lin, ks, cts = tunnel_worst_operands(cref, rp, sp, qs, batch, s_pre is not None, True)(nprng, d_rel, D, gr.n, gs.n)
         pow_out = rng.random() < 0.3
         gs.set_option("tunnel_ep", rng.choice([0, 1]))
         if gadget == "triv": gs.set_option("tunnel_fused", rng.choice([0, 2, 4]))
@@ -69,7 +75,7 @@ def main():
             if not (np.array_equal(got[2 * ct], w0) and np.array_equal(got[2 * ct + 1], w1)):
                 print("MISMATCH", dict(rp=rp, sp=sp, qs=qs, gadget=gadget, batch=batch, pow_out=pow_out, ct=ct, seed=seed)); return 1
         cases += 1
-        key = (gadget, "d_rel %d" % d_rel)
+        key = (gadget, "d_rel %d" % d_rel, "edge moduli" if edges else "drawn moduli", "worst case" if worst else "uniform")
         tally[key] = tally.get(key, 0) + 1
         if cases % 20 == 0: print(f"{cases} cases, {time.time() - t0:.0f} s", flush=True)
     for k in sorted(tally): print(k, tally[k])

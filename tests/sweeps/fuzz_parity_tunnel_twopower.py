@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Randomised parity sweep of alch_ct_tunnel between TWO-POWER rings of the radix-16 engine: random pairs of distinct (and, now and
-then, equal) indices 32 .. 2^13, 1..8 moduli = 1 mod the larger index near 2^28, 2^30, 2^59 or just below 2^62 (32- and 64-bit words), TrivGad or
+then, equal) indices 32 .. 2^13, 1..8 moduli = 1 mod the larger index near 2^28, 2^30, 2^59 or just below 2^62 (32- and 64-bit words) or from the
+ends of the group-size classes of the lazy inner product (helpers.threshold_moduli), TrivGad or
 BaseBGad 2 hints, ciphertexts 0..2 limbs below the hint's ring, random linear functions, hints, ciphertexts, encoding scalars (uniform words, or the
-extreme residues of helpers.extreme_words with s_pre = -1), all four
+extreme residues of helpers.extreme_words with s_pre = -1, or the worst case helpers.tunnel_worst_operands on 32-bit TrivGad cases), all four
 ALCH_POW_IN / ALCH_POW_OUT combinations, batches of 1..9 and a small scratch now and then (several chunks), against the C restatement's
 composition (tests/helpers.py::oracle_tunnel).  usage: tests/sweeps/fuzz_parity_tunnel_twopower.py [seconds] [seed] [max cases]"""
 import os, random, sys, time
@@ -12,7 +13,7 @@ import numpy as np
 import alchemy_amd as A
 from alchemy_amd import capi
 from oracle import cref
-from helpers import extreme_words, oracle_tunnel, primes_1_mod, primes_below
+from helpers import extreme_words, oracle_tunnel, primes_1_mod, primes_below, threshold_moduli, tunnel_worst_operands
 
 
 def main():
@@ -26,13 +27,16 @@ def main():
     while time.time() - t0 < budget and cases < max_cases:
         rp, sp = 1 << rng.randint(5, 13), 1 << rng.randint(5, 13)
         if rp == sp and rng.random() < 0.9: continue
-        lo = rng.choice([1 << 28, 1 << 30, 1 << 30, 1 << 59, 1 << 62])
+        lo = rng.choice([0, 0, 1 << 28, 1 << 30, 1 << 30, 1 << 59, 1 << 62])                  # 0: the class ends
         L = rng.randint(1, 8)
-        qs = primes_below(max(rp, sp), L, 1 << 62) if lo == 1 << 62 else primes_1_mod(max(rp, sp), L, lo=lo)   # 2^62: the last primes BELOW it
+        if lo == 0: qs = threshold_moduli(rng, max(rp, sp), L)
+        else: qs = primes_below(max(rp, sp), L, 1 << 62) if lo == 1 << 62 else primes_1_mod(max(rp, sp), L, lo=lo)   # 2^62: the last primes BELOW it
         if lo < 1 << 31 and max(qs) >= 1 << 31: continue
         dup = rng.choice([0, 0, 1, 2])
         if dup >= L: dup = 0
         gadget = rng.choice(["triv", "triv", "base2"])
+        worst = gadget == "triv" and lo < 1 << 31 and rng.random() < 0.3
+        if worst: dup = 0
         gr, gs = A.Ring(rp, qs), A.Ring(sp, qs)
         gin_ring = A.Ring(rp, qs[dup:]) if dup else gr
         ep, d_rel = A.Tunnel.info(gr, gs)
@@ -43,7 +47,8 @@ def main():
         if extreme: rnd = lambda c, n, ms: extreme_words(nprng, c, n, ms)
         else: rnd = lambda c, n, ms: np.stack([np.stack([nprng.integers(0, q, size=n, dtype=np.int64) for q in ms], axis=1) for _ in range(c)])
         lin, ks, cts = rnd(d_rel, gs.n, qs), rnd(2 * d_rel * D, gs.n, qs), rnd(2 * batch, gr.n, qs[dup:])
-        s_pre = None if rng.random() < 0.5 else [q - 1 for q in qs] if extreme else [rng.randrange(1, q) for q in qs]
+        s_pre = None if rng.random() < 0.5 else [q - 1 for q in qs] if extreme or worst else [rng.randrange(1, q) for q in qs]
+        if worst: lin, ks, cts = tunnel_worst_operands(cref, rp, sp, qs, batch, s_pre is not None, True)(nprng, d_rel, D, gr.n, gs.n)
         flags = rng.choice([0, 0, capi.ALCH_POW_IN, capi.ALCH_POW_OUT, capi.ALCH_POW_IN | capi.ALCH_POW_OUT])
         small_scratch = rng.random() < 0.25
         if small_scratch: gs.set_option("scratch_mib", 1)
@@ -70,7 +75,7 @@ def main():
             print("INPUT MODIFIED", case); return 1
         cases += 1
         key = (gadget, "up" if sp > rp else "down" if rp > sp else "same", "62-bit" if lo == 1 << 62 else "%d-bit" % (64 if lo > 1 << 31 else 32), "dup %d" % dup,
-               "extreme" if extreme else "uniform")
+               "edge moduli" if lo == 0 else "drawn moduli", "worst case" if worst else "extreme" if extreme else "uniform")
         tally[key] = tally.get(key, 0) + 1
         if cases % 20 == 0: print(f"{cases} cases, {time.time() - t0:.0f} s", flush=True)
     for k in sorted(tally): print(k, tally[k])

@@ -13,7 +13,7 @@ import pytest
 
 import alchemy_amd as A
 from alchemy_amd import capi, plaintext
-from helpers import primes_1_mod
+from helpers import group_class_primes, lazy_group, primes_1_mod, primes_below
 from oracle import model_gen as G
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +22,8 @@ pytestmark = pytest.mark.gpu
 def lift_ring(m, kind):
     """two31: two 31-bit primes (32-bit words; k_pt_mac one product at a time); one60: one prime just above 2^59 (64-bit words);
     three29: three primes in (2^29, 2^30) -- lazy groups of K = floor((2^32 - 1) / q) - 2 = 5 products; two20: two primes just above
-    2^20 -- K = 8, the cap."""
+    2^20 -- K = 8, the cap; class3 .. class11: the two largest primes with floor((2^32 - 1) / q) = 3 .. 11, the top of each class of
+    group sizes (K = 0, 2, 3, 4, 5, 6, 7, 8, 8: the least headroom under (K + 2) q < 2^32)."""
     if kind == "two31":
         qs = primes_1_mod(m, 2, 1 << 30)
         assert all((1 << 30) < q < (1 << 31) for q in qs)
@@ -32,6 +33,11 @@ def lift_ring(m, kind):
     elif kind == "three29":
         qs = primes_1_mod(m, 3, 1 << 29)
         assert all(0xFFFFFFFF // q - 2 == 5 for q in qs)
+    elif kind.startswith("class"):
+        kmax = int(kind[5:])
+        qs = primes_below(m, 2, 0xFFFFFFFF // kmax + 1)
+        assert 3 <= kmax <= 11 and qs[0] == group_class_primes(m, kmax)[0]
+        assert all(0xFFFFFFFF // q == kmax and lazy_group(q) == (min(kmax - 2, 8) if kmax >= 4 else 0) for q in qs)
     else:
         qs = primes_1_mod(m, 2, 1 << 20)
         assert all(q < (1 << 21) and 0xFFFFFFFF // q - 2 > 8 for q in qs)

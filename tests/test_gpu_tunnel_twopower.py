@@ -45,11 +45,12 @@ def need_twopower_tunnels():
 
 
 def check_parity(oracle_lib, rp, sp, qs, gadget, batch, with_s_pre, flag_sets=(0,), scratch_mib=None, seed=0, words=rand_elems,
-                 s_pre=None, word_bytes=None):
+                 s_pre=None, word_bytes=None, operands=None):
     """Random linear function, hints and ciphertexts (parity does not need them valid) through Tunnel.apply, every ciphertext
     word for word against oracle_tunnel; every stored word below its modulus; the input buffer is left untouched.
     words(rng, count, n, qs): the word generator (uniform unless given); s_pre: a scalar vector to use instead of a random one;
-    word_bytes: the word size both rings must have."""
+    word_bytes: the word size both rings must have; operands(rng, d_rel, D, n_r, n_s) -> (lin, ks, cts): the operands themselves,
+    instead of three draws from `words` (it runs before anything is uploaded)."""
     L = len(qs)
     gr, gs = A.Ring(rp, qs), A.Ring(sp, qs)
     if word_bytes is not None:
@@ -60,8 +61,12 @@ def check_parity(oracle_lib, rp, sp, qs, gadget, batch, with_s_pre, flag_sets=(0
     assert ep == min(rp, sp) and d_rel == max(1, rp // sp)
     D = gs.gadget_digits(GADGETS[gadget])
     rng = np.random.default_rng(rp * 131 + sp + 7 * L + seed)
-    lin, ks = words(rng, d_rel, gs.n, qs), words(rng, 2 * d_rel * D, gs.n, qs)
-    cts = words(rng, 2 * batch, gr.n, qs)
+    if operands is not None:
+        lin, ks, cts = operands(rng, d_rel, D, gr.n, gs.n)
+        assert lin.shape == (d_rel, gs.n, L) and ks.shape == (2 * d_rel * D, gs.n, L) and cts.shape == (2 * batch, gr.n, L)
+    else:
+        lin, ks = words(rng, d_rel, gs.n, qs), words(rng, 2 * d_rel * D, gs.n, qs)
+        cts = words(rng, 2 * batch, gr.n, qs)
     if s_pre is None:
         s_pre = [int(rng.integers(1, q)) for q in qs] if with_s_pre else None
     want = [oracle_tunnel(oracle_lib, rp, sp, qs, list(lin), list(ks), cts[2 * ct], cts[2 * ct + 1], s_pre, gadget=gadget)
