@@ -42,6 +42,7 @@ SYMBOLS = [
     "alch_buf_add_bcast",
     "alch_ct_add",
     "alch_gauss_table", "alch_gauss_plan", "alch_buf_gauss_dec", "alch_ct_encrypt",
+    "alch_ct_ks_hint", "alch_ct_ks_hint_part",
 ]
 
 
@@ -180,6 +181,9 @@ def load_library():
         "alch_gauss_plan": [C.c_uint32, C.c_uint64, PU64, PU64, C.POINTER(C.c_size_t)],
         "alch_buf_gauss_dec": [VP, C.c_size_t, C.c_size_t, C.c_uint64, VP, C.c_size_t, C.c_uint64, C.c_uint64],
         "alch_ct_encrypt": [VP, C.c_size_t, VP, C.c_size_t, VP, C.c_size_t, C.c_uint64, C.c_uint64],
+        "alch_ct_ks_hint": [VP, C.c_size_t, C.c_int, C.c_size_t, VP, C.c_size_t, VP, C.c_size_t, VP, C.c_size_t, C.c_uint64, C.c_uint64],
+        "alch_ct_ks_hint_part": [VP, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, VP, C.c_size_t, VP, C.c_size_t, VP, C.c_size_t, C.c_uint64,
+                                 C.c_uint64],
     }
     for name, args in sig.items():
         fn = getattr(l, name)

@@ -4337,6 +4337,72 @@ extern "C" int alch_ct_encrypt(alch_buf* out, size_t batch, const alch_buf* err_
     return ALCH_BY_WORD(r, do_ct_encrypt, r, out->dptr, batch, e, sk, seed, ct0);
 } catch (...) { return abi_catch(); }
 
+template <typename W>
+static int do_ct_ks_hint(alch_ring* r, const hintgad::Layout& G, void* out, size_t e_first, size_t e_count, const void* v, const void* err,
+                         const void* sk, uint64_t seed, uint64_t ct0) {
+    const DevRing<W>& R = dev_ring<W>(r);
+    const size_t words = e_count * elem_words(r);
+    W* o = reinterpret_cast<W*>(out);
+    const W *x = reinterpret_cast<const W*>(v), *e = reinterpret_cast<const W*>(err), *s = reinterpret_cast<const W*>(sk);
+    ALCH_LAUNCH_VW(k_ct_ks_hint, r, words, r->stream, R, G, o, x, e, s, words, (u64)e_first, seed, ct0);
+    HIP_TRY(hipGetLastError());
+    return ALCH_OK;
+}
+
+// The hint of the values v_crt[v_first ..]: all of it (whole: n_v values, entries 0 .. n_v D) or its entries [e_first, e_first + e_count).
+// `name`: the entry point, for the messages.
+static int ct_ks_hint(const char* name, bool whole, alch_buf* out, size_t out_first, int gadget, size_t e_first, size_t e_count, size_t n_v,
+                      const alch_buf* v_crt, size_t v_first, const alch_buf* err_crt, size_t err_first, const alch_buf* sk_crt,
+                      size_t sk_index, uint64_t seed, uint64_t ct0) {
+    const std::string who(name);
+    if (!out || !v_crt || !err_crt || !sk_crt) return fail(ALCH_E_INVALID, who + ": null buffer");
+    alch_ring* r = out->ring;
+    BIND(r);
+    if (v_crt->ring != r || err_crt->ring != r || sk_crt->ring != r)
+        return fail(ALCH_E_INVALID, who + ": the values, the error terms and the key must belong to the output's ring");
+    if (gadget != ALCH_GAD_TRIV && gadget != ALCH_GAD_BASE2) return fail(ALCH_E_INVALID, who + ": unknown gadget");
+    const hintgad::Layout G = hintgad::make_layout(r->q, r->L, gadget == ALCH_GAD_BASE2);
+    const size_t D = G.D;
+    if (D == 0) return fail(ALCH_E_INVALID, who + ": the gadget has no entries on this ring");
+    if (whole) {
+        if (n_v > out->n_elems / (2 * D)) return fail(ALCH_E_INVALID, who + ": the output range must hold 2 * n_v * (gadget entries) ring elements");
+        e_count = n_v * D;
+    } else {                                                 // the values the part's entries belong to
+        if (!pairs_ok(e_count, out->n_elems) || e_first > (size_t)-1 - e_count) return fail(ALCH_E_INVALID, who + ": the output range must hold 2 * e_count ring elements");
+        n_v = e_count ? (e_first + e_count - 1) / D + 1 : 0;
+    }
+    if (!pairs_ok(e_count, out->n_elems) || !range_ok(out_first, 2 * e_count, out->n_elems))
+        return fail(ALCH_E_INVALID, who + ": the output range must hold 2 ring elements per entry");
+    if (!range_ok(v_first, n_v, v_crt->n_elems)) return fail(ALCH_E_INVALID, who + ": value range out of bounds");
+    if (!range_ok(err_first, e_count, err_crt->n_elems)) return fail(ALCH_E_INVALID, who + ": error-term range out of bounds");
+    if (sk_index >= sk_crt->n_elems) return fail(ALCH_E_INVALID, who + ": key index out of bounds");
+    if (!r->has_crt) return fail(ALCH_E_NO_CRT, who + ": this ring has no CRT basis (created with alch_ring_create_nocrt)");
+    if (e_count == 0) return ALCH_OK;
+    const size_t eb = elem_bytes(r);
+    void* o = reinterpret_cast<char*>(out->dptr) + out_first * eb;
+    const void* v = reinterpret_cast<const char*>(v_crt->dptr) + v_first * eb;
+    const void* e = reinterpret_cast<const char*>(err_crt->dptr) + err_first * eb;
+    const void* sk = reinterpret_cast<const char*>(sk_crt->dptr) + sk_index * eb;
+    if (bytes_overlap(o, 2 * e_count * eb, v, n_v * eb) || bytes_overlap(o, 2 * e_count * eb, e, e_count * eb) ||
+        bytes_overlap(o, 2 * e_count * eb, sk, eb))
+        return fail(ALCH_E_INVALID, who + ": the output overlaps an input");
+    return ALCH_BY_WORD(r, do_ct_ks_hint, r, G, o, e_first, e_count, v, e, sk, seed, ct0);
+}
+
+extern "C" int alch_ct_ks_hint(alch_buf* out, size_t out_first, int gadget, size_t n_v, const alch_buf* v_crt, size_t v_first,
+                               const alch_buf* err_crt, size_t err_first, const alch_buf* sk_crt, size_t sk_index, uint64_t seed,
+                               uint64_t ct0) try {
+    return ct_ks_hint("alch_ct_ks_hint", true, out, out_first, gadget, 0, 0, n_v, v_crt, v_first, err_crt, err_first, sk_crt, sk_index,
+                      seed, ct0);
+} catch (...) { return abi_catch(); }
+
+extern "C" int alch_ct_ks_hint_part(alch_buf* out, size_t out_first, int gadget, size_t e_first, size_t e_count, const alch_buf* v_crt,
+                                    size_t v_first, const alch_buf* err_crt, size_t err_first, const alch_buf* sk_crt, size_t sk_index,
+                                    uint64_t seed, uint64_t ct0) try {
+    return ct_ks_hint("alch_ct_ks_hint_part", false, out, out_first, gadget, e_first, e_count, 0, v_crt, v_first, err_crt, err_first, sk_crt,
+                      sk_index, seed, ct0);
+} catch (...) { return abi_catch(); }
+
 // ------------------------------------------------------------------------------------------------------
 // plaintext-side mul_, div2_ and linearCyc_ on resident batches (Eval.hs:65-67, 72-88, 136-148): kernel_plain.hpp
 // ------------------------------------------------------------------------------------------------------

@@ -7,9 +7,11 @@
 //   k_gauss_axis<P>   the Cholesky factor of P I - J along one odd axis of the scratch: one lane per column, column in registers
 //   k_gauss_round     scratch doubles -> (coset) rounding -> residues of every limb, limb-major
 //   k_ct_encrypt      c1 = the uniform words of alch_buf_fill_uniform's odd elements, c0 = err - c1 s, one pass on the CRT basis
+//   k_ct_ks_hint      the same pass per gadget entry with g_t v added: key-switch and tunnel hints (alch_ct_ks_hint)
 #pragma once
 
 #include "gauss_sampler.hpp"
+#include "hint_gadget.hpp"
 
 namespace alch {
 
@@ -113,6 +115,45 @@ __global__ void k_ct_encrypt(DevRing<W> R, W* out, const W* err, const W* sk, si
         const size_t o = w + wk.outer * ev;                  // component 0 of ciphertext wk.outer, same limb and position
         reinterpret_cast<P*>(out)[o] = c0;
         reinterpret_cast<P*>(out)[o + ev] = c1;
+    }
+}
+
+// ---- key-switch and tunnel hints (ksHint, KeysHints.hs:101-129), ring arithmetic ---------------------------------------------
+// For value i and gadget entry t < D, e = i D + t: out[2e + 1] = a, uniform words by k_ct_encrypt's rule; out[2e] = g_t v[i] + err[e] - a s.
+// g_t is 2^d(t) on limb i(t) and 0 elsewhere (hint_gadget.hpp), so v is read on one limb of every entry only.  One launch serves the
+// entries [e0, e0 + count): out, err and the counter ct0 are those of entry e0, v is value 0.  Walked as [i][t L + j][k] from the
+// position of entry e0: t and j come from one 32-bit division, i never needs a 64-bit one.  words = count L n.
+template <typename W, int VW>
+__global__ void k_ct_ks_hint(DevRing<W> R, hintgad::Layout G, W* out, const W* v, const W* err, const W* sk, size_t words, u64 e0,
+                             u64 seed, u64 ct0) {
+    typedef Pack<W, VW> P;
+    const u32 nv = R.n / VW, L = (u32)R.L;
+    const size_t ev = (size_t)L * nv;                        // packs per ring element
+    Walk3 wk(blockIdx.x * (size_t)blockDim.x + threadIdx.x + (size_t)e0 * ev, (size_t)gridDim.x * blockDim.x, nv, G.D * L);
+    ALCH_WALK(w, words / VW, wk) {
+        const u32 t = wk.mid / L, j = wk.mid - t * L;
+        const ModP<W> m = R.mod[j];
+        const u64 e = (u64)wk.outer * G.D + t - e0;          // entry of this launch
+        const P s = reinterpret_cast<const P*>(sk)[(size_t)j * nv + wk.k];
+        P h0 = reinterpret_cast<const P*>(err)[w], h1;
+        u32 gl, gd;
+        hintgad::entry(G, t, gl, gd);
+        if (gl == j) {
+            const W g = mont_mul((W)((W)1 << gd), m.r2, m);  // 2^d < q_j, to Montgomery form
+            const P x = reinterpret_cast<const P*>(v)[(wk.outer * L + j) * nv + wk.k];
+#pragma unroll
+            for (int c = 0; c < VW; ++c) h0.v[c] = add_mod(h0.v[c], mont_mul(x.v[c], g, m), m.q);
+        }
+        const u64 pos = hintgad::odd_word_pos(ct0 + e, L, j, R.n, wk.k * VW);
+#pragma unroll
+        for (int c = 0; c < VW; ++c) {
+            const W u = (W)(splitmix64(seed + pos + (u64)c) % (u64)m.q);
+            h1.v[c] = u;
+            h0.v[c] = sub_mod(h0.v[c], mont_mul(u, mont_mul(s.v[c], m.r2, m), m), m.q);
+        }
+        const size_t o = w + (size_t)e * ev;                 // component 0 of pair e, same limb and position
+        reinterpret_cast<P*>(out)[o] = h0;
+        reinterpret_cast<P*>(out)[o + ev] = h1;
     }
 }
 

@@ -5,7 +5,8 @@
 //   SK, genSK                                (KeysHints.hs:86-96:  svar = r / sqrt(phi(m')))
 //   encrypt, decrypt, errorTermUnrestricted   (PT2CT.hs:84-99, Eval.hs:151-160); decryptBatch / errorRatesBatch on resident batches
 //   toLSD / toMSD, (*), addPublic, mulPublic, modSwitchPT, modSwitch, keySwitchQuadCirc, tunnel   (Eval.hs:65-67,129-134)
-//   ksQuadCircHint, tunnelHint               (KeysHints.hs:101-129)
+//   ksQuadCircHint, tunnelHint               (KeysHints.hs:101-129); ksHintDevice / ksQuadCircHintDevice / tunnelHintDevice make the
+//                                            same hints on resident buffers (alch_ct_ks_hint), from counter-based streams
 //
 // REPLAY AND TEST CODE, NOT A KEY GENERATOR: randomness comes from a caller-supplied std::mt19937_64 (reproducible runs) and uniform
 // residues are drawn as `rng() % q` -- not a CSPRNG, with the 2^-33 modulo bias of a 31-bit q in a 64-bit draw.  A production host
@@ -548,7 +549,111 @@ struct DevTunnel {
     ~DevTunnel() { if (t) alch_tunnel_free(t); }
 };
 
-// PT2CT's linearCyc_ on batches (PT2CT.hs:207-229): modSwitch_ .: tunnel_ hint .: modSwitch_.  x lives on the last limbs of the
+// ---- hints generated on resident buffers (alch_ct_ks_hint; the host forms above are the reference) ----------------------------------
+// Same entry points and same seed rule as alchemy_amd/hints.py (ks_hint, ks_quad_circ_hint, tunnel_hint), so both give the same
+// words: the Gaussian stream is splitmix64(seed), the uniform stream splitmix64(seed + 1); counter-based, another stream than the
+// host forms' mt19937_64.  Keys arrive as one CRT-basis element in HBM (keyToDevice), uploaded once by the caller.
+struct DevBufs {                                    // frees what it holds, in any order, on every way out
+    std::vector<alch_buf*> b;
+    alch_buf* alloc(const Ring& r, size_t n) {
+        alch_buf* x = nullptr;
+        check(alch_buf_alloc(r.handle(), n, &x), "alch_buf_alloc");
+        b.push_back(x);
+        return x;
+    }
+    alch_buf* release(alch_buf* x) { b.erase(std::find(b.begin(), b.end(), x)); return x; }
+    ~DevBufs() { for (alch_buf* x : b) alch_buf_free(x); }
+};
+
+inline size_t gadgetDigits(const Ring& r, int gadget) {
+    if (gadget == ALCH_GAD_TRIV) return (size_t)r.L();
+    int nd = 0;
+    check(alch_decompose_base2(r.handle(), nullptr, nullptr, &nd), "alch_decompose_base2");
+    return (size_t)nd;
+}
+
+// ksHint for the values v_crt[0 .. n_v) under the key: 2 n_v D elements on the CRT basis, order value, gadget entry, (b, a); the
+// caller frees the buffer.  Error terms of more than chunk_bytes are made, and used, in parts.
+inline alch_buf* ksHintDevice(const Ring& r, int gadget, const alch_buf* sk_crt, const alch_buf* v_crt, size_t n_v, double svar, uint64_t seed,
+                              size_t chunk_bytes = (size_t)256 << 20) {
+    const size_t D = gadgetDigits(r, gadget), total = n_v * D;
+    uint32_t n = 0; int L = 0, word = 0;
+    check(alch_ring_n(r.handle(), &n, &L, &word), "alch_ring_n");
+    const size_t chunk = std::max<size_t>(1, chunk_bytes / ((size_t)n * (size_t)L * (size_t)word));
+    DevBufs own;
+    alch_buf *out = own.alloc(r, std::max<size_t>(1, 2 * total)), *err = own.alloc(r, std::max<size_t>(1, std::min(chunk, total)));
+    uint64_t svar_bits;
+    memcpy(&svar_bits, &svar, sizeof svar_bits);
+    const uint64_t g_seed = alch::gauss::mix64(seed), u_seed = alch::gauss::mix64(seed + 1);
+    for (size_t done = 0; done < total; done += chunk) {
+        const size_t now = std::min(chunk, total - done);
+        check(alch_buf_gauss_dec(err, 0, now, svar_bits, nullptr, 0, g_seed, (uint64_t)done), "alch_buf_gauss_dec");
+        check(alch_buf_l(err, 0, now), "alch_buf_l");
+        check(alch_buf_crt(err, 0, now), "alch_buf_crt");
+        if (now == total) check(alch_ct_ks_hint(out, 0, gadget, n_v, v_crt, 0, err, 0, sk_crt, 0, u_seed, 0), "alch_ct_ks_hint");
+        else check(alch_ct_ks_hint_part(out, 2 * done, gadget, done, now, v_crt, 0, err, 0, sk_crt, 0, u_seed, (uint64_t)done), "alch_ct_ks_hint_part");
+    }
+    return own.release(out);
+}
+
+// ksQuadCircHint: v = s * s, ksHint, alch_hint_from_buf
+inline DevQuadHint ksQuadCircHintDevice(const Ring& r, int gadget, const alch_buf* sk_crt, double svar, uint64_t seed) {
+    DevBufs own;
+    alch_buf* s2 = own.alloc(r, 1);
+    check(alch_buf_mul(s2, sk_crt, sk_crt, 1), "alch_buf_mul");
+    own.b.push_back(ksHintDevice(r, gadget, sk_crt, s2, 1, svar, seed));
+    DevQuadHint d;
+    d.ring = &r;
+    check(alch_hint_from_buf(r.handle(), gadget, own.b.back(), &d.h), "alch_hint_from_buf");
+    return d;
+}
+
+inline void cycToBuf(alch_buf* dst, size_t index, const Cyc& x_) {
+    const Cyc x = x_.toCRT();
+    if (x.onDeviceOnly()) check(alch_buf_copy(dst, index, x.dev(), 0, 1), "alch_buf_copy");
+    else check(alch_buf_upload(dst, index, 1, x.data().data()), "alch_buf_upload");
+}
+
+// tunnelHint f skout skin.  The values v_i = f'(s_in p_i) come from the tunnel entry point itself: a provisional tunnel with an
+// all-zero hint sends the ciphertext (s_in p_i, 0) to (f'(s_in p_i), 0).  Then ksHint with n_v = d_rel under s_out -- its output is
+// the ks_crt of alch_tunnel_create as it stands.  sk_in_crt lives on the ring (rp, qs), sk_out_crt on (sp, qs).
+inline DevTunnel tunnelHintDevice(RingCache& rc, PtOps& ops, const Linear& f, uint32_t rp, uint32_t sp, const std::vector<uint64_t>& qs,
+                                  const alch_buf* sk_out_crt, const alch_buf* sk_in_crt, double svar, uint64_t seed, int gadget = ALCH_GAD_TRIV) {
+    const Ring &rr = rc.get(rp, qs), &rs = rc.get(sp, qs);
+    uint32_t ep = 0, d_rel = 0;
+    check(alch_tunnel_info(rr.handle(), rs.handle(), &ep, &d_rel), "alch_tunnel_info");
+    if (d_rel != f.ys.size()) throw std::runtime_error("tunnelHintDevice: the linear function does not match the rings");
+    const size_t d = d_rel, L = (size_t)rs.L(), ne = totient(ep);
+    DevBufs own;
+    alch_buf *lin = own.alloc(rs, d), *zero = own.alloc(rs, 2 * d * L), *cin = own.alloc(rr, 2 * d), *prod = own.alloc(rr, 2 * d),
+             *cout = own.alloc(rs, 2 * d), *v = own.alloc(rs, d);
+    for (size_t i = 0; i < d; ++i) cycToBuf(lin, i, liftEmbed(ops, rs, f.ys[i]));
+    const std::vector<uint64_t> zeros(L, 0);
+    check(alch_buf_scale(zero, zero, 2 * d * L, zeros.data()), "alch_buf_scale");
+    // relative powerful basis of R'/E': unit vectors at the positions table ALCH_EXT_COEFFS lists first
+    size_t len = d * ne;
+    std::vector<int32_t> tab(len);
+    check(alch_ext_table(ep, rp, ALCH_EXT_COEFFS, tab.data(), &len), "alch_ext_table");
+    std::vector<int64_t> units(2 * d * (size_t)rr.n() * L, 0);
+    for (size_t i = 0; i < d; ++i)
+        for (size_t j = 0; j < L; ++j) units[(2 * i * (size_t)rr.n() + (size_t)tab[i * ne]) * L + j] = 1;
+    check(alch_buf_upload(cin, 0, 2 * d, units.data()), "alch_buf_upload");
+    check(alch_buf_crt(cin, 0, 2 * d), "alch_buf_crt");
+    check(alch_buf_mul_public(prod, cin, sk_in_crt, 0, 2 * d), "alch_buf_mul_public");                  // (s_in p_i, 0)
+    {
+        DevTunnel probe;
+        probe.rr = &rr; probe.rs = &rs;
+        check(alch_tunnel_create(rr.handle(), rs.handle(), ALCH_GAD_TRIV, lin, zero, &probe.t), "alch_tunnel_create");
+        check(alch_ct_tunnel(probe.t, prod, cout, d, nullptr, 0), "alch_ct_tunnel");
+        for (size_t i = 0; i < d; ++i) check(alch_buf_copy(v, i, cout, 2 * i, 1), "alch_buf_copy");
+    }
+    own.b.push_back(ksHintDevice(rs, gadget, sk_out_crt, v, d, svar, seed));
+    DevTunnel out;
+    out.rr = &rr; out.rs = &rs;
+    check(alch_tunnel_create(rr.handle(), rs.handle(), gadget, lin, own.b.back(), &out.t), "alch_tunnel_create");
+    return out;
+}
+
 // tunnel's R' ring (the leading modSwitch up is part of alch_ct_tunnel); the result is rescaled down to rout.
 inline DevBatch tunnelBatch(const DevTunnel& tun, DevBatch& x, const Ring& rout, uint32_t m_out) {
     if (x.k != 0) throw std::runtime_error("tunnelBatch: k must be 0");

@@ -14,6 +14,11 @@
 //
 //   homomrlwr_replay [batch] [--seed N] [--dump DIR] [--per-element] [--per-element-resident] [--per-element-zip-host]
 //                    [--host-mode buffers|resident] [--var-scale F] [--quiet-stages] [--device-decrypt] [--device-plaintext] [--device-encrypt]
+//                    [--device-hints]
+// --device-hints builds the five tunnel hints and the four quadratic hints on resident buffers -- tunnelHintDevice / ksQuadCircHintDevice
+// over alch_buf_gauss_dec, l / crt and alch_ct_ks_hint, the counter-based streams seeded from --seed, the genSK keys uploaded once per
+// ring -- instead of one gadget entry at a time on the host; every later line is the same.  Not with the --per-element* flags, which
+// replay the first hop from the host form of its hint.
 // --device-encrypt encrypts the RLWR secret through encryptBatch -- embed / lInv, alch_buf_gauss_dec, l / crt and alch_ct_encrypt on a
 // resident plaintext batch, the counter-based sampler seeded from --seed -- instead of the host-side encrypt; the closing check is unchanged.
 // --device-plaintext computes the plaintext side (eval ringRound (s * a)) on resident batches -- PtBatch over alch_pt_mul, alch_pt_eval_lin,
@@ -62,7 +67,7 @@ int main(int argc, char** argv) {
     size_t B = 4;
     uint64_t seed = 2026;
     std::string dump;
-    bool per_element = false, per_resident = false, per_ziphost = false, quiet = false, device_decrypt = false, device_plaintext = false, device_encrypt = false;
+    bool per_element = false, per_resident = false, per_ziphost = false, quiet = false, device_decrypt = false, device_plaintext = false, device_encrypt = false, device_hints = false;
     double var_scale = 1.0;
     Mode host_mode = Mode::Resident;
     for (int i = 1; i < argc; ++i) {
@@ -75,12 +80,17 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--device-decrypt")) device_decrypt = true;
         else if (!strcmp(argv[i], "--device-plaintext")) device_plaintext = true;
         else if (!strcmp(argv[i], "--device-encrypt")) device_encrypt = true;
+        else if (!strcmp(argv[i], "--device-hints")) device_hints = true;
         else if (!strcmp(argv[i], "--var-scale") && i + 1 < argc) var_scale = atof(argv[++i]);
         else if (!strcmp(argv[i], "--host-mode") && i + 1 < argc) host_mode = !strcmp(argv[++i], "buffers") ? Mode::HostBuffers : Mode::Resident;
         else B = (size_t)atoi(argv[i]);
     }
     const double R_GAUSS = 5.0 * var_scale;                       // examples/HomomRLWR.hs:56
     mode() = host_mode;
+    if (device_hints && (per_element || per_resident || per_ziphost)) {
+        fprintf(stderr, "error: --device-hints keeps no host form of the hints; the --per-element* flags need one\n");
+        return 2;
+    }
     try {
         std::mt19937_64 rng(seed);
         RingCache rc;
@@ -104,15 +114,37 @@ int main(int argc, char** argv) {
         for (int k = 0; k < 5; ++k) lin.push_back(decToCRT(ops, H[k], H[k + 1], 2, K_EXP));
         std::vector<DevTunnel> dtun;
         std::vector<TunnelHint> thints;
-        for (int k = 0; k < 5; ++k) {
-            const std::vector<uint64_t> qs = moduli(tuns[k].lh);
-            thints.push_back(tunnelHint(rc, ops, lin[k], HP[k], HP[k + 1], qs, sk[k + 1], sk[k], rng));
-            dtun.emplace_back(rc.get(HP[k], qs), rc.get(HP[k + 1], qs), thints.back());
-        }
         std::vector<DevQuadHint> dquad;
-        for (int i = 0; i < 4; ++i) {
-            const Ring& rh = rc.get(HP[5], moduli(muls[i].lh));
-            dquad.emplace_back(rh, ksQuadCircHint(rc, rh, sk[5], rng));
+        if (device_hints) {
+            // every key once per ring it is used on, as one CRT-basis element in HBM; hint j draws from the streams of seed + 16 + 2 j
+            std::map<const Ring*, alch_buf*> keys;
+            auto key = [&](const Ring& r, int k) { auto it = keys.find(&r); return it != keys.end() ? it->second : (keys[&r] = keyToDevice(r, sk[k])); };
+            try {
+                for (int k = 0; k < 5; ++k) {
+                    const std::vector<uint64_t> qs = moduli(tuns[k].lh);
+                    dtun.push_back(tunnelHintDevice(rc, ops, lin[k], HP[k], HP[k + 1], qs, key(rc.get(HP[k + 1], qs), k + 1), key(rc.get(HP[k], qs), k),
+                                                    sk[k + 1].svar, seed + 16 + 2 * (uint64_t)k));
+                }
+                for (int i = 0; i < 4; ++i) {
+                    const Ring& rh = rc.get(HP[5], moduli(muls[i].lh));
+                    dquad.push_back(ksQuadCircHintDevice(rh, ALCH_GAD_TRIV, key(rh, 5), sk[5].svar, seed + 26 + 2 * (uint64_t)i));
+                    check(alch_sync(rh.handle()), "alch_sync");
+                }
+            } catch (...) {
+                for (auto& kv : keys) alch_buf_free(kv.second);
+                throw;
+            }
+            for (auto& kv : keys) alch_buf_free(kv.second);
+        } else {
+            for (int k = 0; k < 5; ++k) {
+                const std::vector<uint64_t> qs = moduli(tuns[k].lh);
+                thints.push_back(tunnelHint(rc, ops, lin[k], HP[k], HP[k + 1], qs, sk[k + 1], sk[k], rng));
+                dtun.emplace_back(rc.get(HP[k], qs), rc.get(HP[k + 1], qs), thints.back());
+            }
+            for (int i = 0; i < 4; ++i) {
+                const Ring& rh = rc.get(HP[5], moduli(muls[i].lh));
+                dquad.emplace_back(rh, ksQuadCircHint(rc, rh, sk[5], rng));
+            }
         }
         // the RLWR secret s (encrypted) and the public a's
         auto randPt = [&](uint32_t m) { PtCyc x{m, P, Basis::Pow, std::vector<int64_t>(totient(m))}; for (auto& v : x.v) v = (int64_t)(rng() % (uint64_t)P); return x; };

@@ -155,3 +155,7 @@ foreign import ccall safe   "alch_gauss_table"         c_gaussTable      :: Ptr 
 foreign import ccall safe   "alch_gauss_plan"          c_gaussPlan       :: Word32 -> Word64 -> Ptr Word64 -> Ptr Word64 -> Ptr CSize -> IO CInt
 foreign import ccall safe   "alch_buf_gauss_dec"       c_bufGaussDec     :: Ptr AlchBuf -> CSize -> CSize -> Word64 -> Ptr AlchBuf -> CSize -> Word64 -> Word64 -> IO CInt
 foreign import ccall safe   "alch_ct_encrypt"          c_ctEncrypt       :: Ptr AlchBuf -> CSize -> Ptr AlchBuf -> CSize -> Ptr AlchBuf -> CSize -> Word64 -> Word64 -> IO CInt
+-- key-switch and tunnel hints on resident buffers (added within library version 1.8): ksHint's ring arithmetic per gadget entry, whole
+-- or in parts
+foreign import ccall safe   "alch_ct_ks_hint"          c_ctKsHint        :: Ptr AlchBuf -> CSize -> CInt -> CSize -> Ptr AlchBuf -> CSize -> Ptr AlchBuf -> CSize -> Ptr AlchBuf -> CSize -> Word64 -> Word64 -> IO CInt
+foreign import ccall safe   "alch_ct_ks_hint_part"     c_ctKsHintPart    :: Ptr AlchBuf -> CSize -> CInt -> CSize -> CSize -> Ptr AlchBuf -> CSize -> Ptr AlchBuf -> CSize -> Ptr AlchBuf -> CSize -> Word64 -> Word64 -> IO CInt

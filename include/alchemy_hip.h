@@ -597,6 +597,30 @@ int alch_buf_gauss_dec(alch_buf *dst, size_t first, size_t count, uint64_t svar_
 int alch_ct_encrypt(alch_buf *out, size_t batch, const alch_buf *err_crt, size_t err_first, const alch_buf *sk_crt, size_t sk_index,
                     uint64_t seed, uint64_t ct0);
 
+/* ---- key-switch and tunnel hints on resident buffers (added within 1.8; probe for the symbol) --------------------------------------
+ * ksHint (KeysHints.hs:101-129): for every value v_i and every gadget entry t an RLWE sample under the key with g_t v_i added.  The
+ * gadget has D entries: D = L for ALCH_GAD_TRIV, D = sum_i ceil(log2 q_i) for ALCH_GAD_BASE2, the digits of limb 0 first, least
+ * significant first (the order of alch_hint_load and alch_decompose_base2).  Entry t belongs to limb i(t) with exponent d(t) (0 for
+ * TrivGad): g_t is 2^d(t) on limb i(t) and 0 on every other limb.  For i < n_v, t < D and e = i D + t, everything on the CRT basis of
+ * one ring:
+ *   out[out_first + 2e + 1] = a, word (limb j, slot k) = splitmix64(seed + ((2 (ct0 + e) + 1) L + j) n + k) mod q_j  (alch_ct_encrypt's
+ *                             rule: ct0 cuts a long hint into chunks the same way)
+ *   out[out_first + 2e]     = g_t v_crt[v_first + i] + err_crt[err_first + e] - a * sk_crt[sk_index]
+ * n_v = 1 gives the layout of alch_hint_from_buf (h0_0, h1_0, h0_1, ...), n_v = d_rel the ks_crt of alch_tunnel_create.  The error
+ * terms are the caller's (alch_buf_gauss_dec, l, crt).  splitmix64 is a STATISTICAL generator, not a cryptographic one.
+ * n_v = 0: ALCH_OK, nothing queued.  ALCH_E_INVALID: null buffer; buffers of different rings; unknown gadget; a range or the key index
+ * outside its buffer; the output range overlapping an input.  ALCH_E_NO_CRT: a ring without CRT basis. */
+int alch_ct_ks_hint(alch_buf *out, size_t out_first, int gadget, size_t n_v, const alch_buf *v_crt, size_t v_first,
+                    const alch_buf *err_crt, size_t err_first, const alch_buf *sk_crt, size_t sk_index, uint64_t seed, uint64_t ct0);
+/* A part of the same hint, for callers that cannot hold every error term at once: the entries e_first <= e < e_first + e_count of the
+ * hint of the values v_crt[v_first ..] (entry e belongs to value e / D and gadget entry e mod D; any cut, not only a multiple of D).
+ * out_first, err_first and ct0 are those of entry e_first: out[out_first + 2 (e - e_first)], err_crt[err_first + e - e_first],
+ * counter ct0 + e - e_first.  Consecutive parts with out_first, err_first and ct0 advanced by the entries done give the words of one
+ * alch_ct_ks_hint call.  Statuses as above; v_crt must hold the values of every entry of the part. */
+int alch_ct_ks_hint_part(alch_buf *out, size_t out_first, int gadget, size_t e_first, size_t e_count, const alch_buf *v_crt,
+                         size_t v_first, const alch_buf *err_crt, size_t err_first, const alch_buf *sk_crt, size_t sk_index,
+                         uint64_t seed, uint64_t ct0);
+
 /* ---- modSwitch building block (Eval.hs:130) ---------------------------------------
  * Rescale (a,b) -> b on Pow-basis elements: src lives in ring_src (L limbs), dst in ring_dst whose
  * limbs are ring_src's limbs 1..L-1:  dst_j = q_0^-1 * (src_j - reduce(lift src_0)). */
