@@ -276,7 +276,14 @@ class Ring:
 
     # --- stream / timing
     def set_stream(self, hip_stream: int):
+        """Queue this ring's work on a caller-owned hipStream_t from now on (torch: `stream.cuda_stream`); 0 is the null stream."""
         _check(self._l.alch_ring_set_stream(self._h, C.c_void_p(hip_stream)))
+
+    def device_stream(self):
+        """(HIP device, hipStream_t as an int) the ring queues its work on (alch_ring_device); 0 is the null stream."""
+        dev, s = C.c_int(), C.c_void_p()
+        _check(self._l.alch_ring_device(self._h, C.byref(dev), C.byref(s)))
+        return int(dev.value), int(s.value or 0)
 
     def share_stream(self, other: "Ring"):
         """Queue this ring's work on `other`'s stream from now on (operations between the two rings then need no events)."""

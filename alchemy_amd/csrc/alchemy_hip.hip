@@ -1605,7 +1605,7 @@ extern "C" int alch_ring_destroy(alch_ring* r) try {
     ALCH_DEVICE_LOCK(r->device);
     (void)hipSetDevice(r->device);
     if (r->scratch) { alch_buf* b = r->scratch; r->scratch = nullptr; (void)hipFree(b->dptr); delete b; }
-    if (r->stream) (void)hipStreamSynchronize(r->stream);
+    (void)hipStreamSynchronize(r->stream);         // whichever stream it is: the null stream is a stream like any other
     for (auto& e : r->pool) (void)hipFree(e.second);
     r->pool.clear();
     for (auto& pn : r->pin) { if (pn.p) (void)hipHostFree(pn.p); if (pn.ev) (void)hipEventDestroy(pn.ev); pn = alch_ring::Pin(); }
@@ -1789,8 +1789,11 @@ static int launch(const GenCall<W>& g, const char* what) {
 
 template <typename W>
 static int do_crt(alch_ring* r, void* data, size_t first_elem, size_t count, bool inverse, const void* src = nullptr,
-                  hipStream_t stream = nullptr) {
+                  const alch_ring* on = nullptr) {
     // src != null: transform src[first_elem ..) into data[first_elem ..) (LDS-resident sizes only)
+    // on != null: queue on that ring's stream, whatever stream that is (the null stream included) -- the call is part of that ring's
+    // pipeline; a ring, never a hipStream_t: a stream handle has no value that can stand for "not given"
+    const hipStream_t stream = (on ? on : r)->stream;
     if (count == 0) return ALCH_OK;
     if (!r->has_crt) return fail(ALCH_E_NO_CRT, "this ring has no CRT basis (created with alch_ring_create_nocrt)");
     if (r->gen) {
@@ -1798,7 +1801,7 @@ static int do_crt(alch_ring* r, void* data, size_t first_elem, size_t count, boo
         g.op = inverse ? GEN_CRTINV : GEN_CRT;
         g.ring = &dev_ring<W>(r);
         g.gen = &gen_dev<W>(r);
-        g.stream = stream ? stream : r->stream;
+        g.stream = stream;
         g.data = reinterpret_cast<W*>(data);
         g.src = reinterpret_cast<const W*>(src);
         const size_t polys = count * (size_t)r->L;
@@ -1815,7 +1818,7 @@ static int do_crt(alch_ring* r, void* data, size_t first_elem, size_t count, boo
     c.src = reinterpret_cast<const W*>(src);
     c.op = inverse ? OP_CRTINV : OP_CRT;
     c.ring = &dev_ring<W>(r);
-    c.stream = stream ? stream : r->stream;     // another ring's stream when the call is part of that ring's pipeline
+    c.stream = stream;
     c.data = reinterpret_cast<W*>(data);
     const size_t polys = count * (size_t)r->L;
     // grids are 32-bit: split very large batches
@@ -2352,16 +2355,16 @@ extern "C" int alch_ct_add_public(alch_buf* dst, const alch_buf* src, size_t bat
 // ------------------------------------------------------------------------------------------------------
 // Runs one column operator (kernel_gen.hpp) on elements first, first + stride, ... (count of them) of `data`.
 template <typename W>
-static int do_columns(alch_ring* r, GenOp op, void* data, size_t first, size_t count, size_t stride, hipStream_t stream = nullptr,
+static int do_columns(alch_ring* r, GenOp op, void* data, size_t first, size_t count, size_t stride, const alch_ring* on = nullptr,
                       const void* src = nullptr) {
-    // src != null: out of place, src[e] -> data[e] (same element layout and stride)
+    // src != null: out of place, src[e] -> data[e] (same element layout and stride); on != null: queue on that ring's stream (do_crt)
     if (count == 0) return ALCH_OK;
     GenCall<W> g{};
     g.src = reinterpret_cast<const W*>(src);
     g.op = op;
     g.ring = &dev_ring<W>(r);
     g.gen = &gen_dev<W>(r);
-    g.stream = stream ? stream : r->stream;
+    g.stream = (on ? on : r)->stream;
     g.data = reinterpret_cast<W*>(data);
     g.elem_stride = stride;
     g.zdom = r->zdom;
@@ -2376,9 +2379,9 @@ static int do_columns(alch_ring* r, GenOp op, void* data, size_t first, size_t c
     return ALCH_OK;
 }
 
-static int columns(alch_ring* r, GenOp op, void* data, size_t first, size_t count, size_t stride, hipStream_t stream = nullptr,
+static int columns(alch_ring* r, GenOp op, void* data, size_t first, size_t count, size_t stride, const alch_ring* on = nullptr,
                    const void* src = nullptr) {
-    return ALCH_BY_WORD(r, do_columns, r, op, data, first, count, stride, stream, src);
+    return ALCH_BY_WORD(r, do_columns, r, op, data, first, count, stride, on, src);
 }
 
 // mulG (divide = false) or divG on elements [first, first + count) of a buffer, basis ALCH_BASIS_*.
@@ -3271,8 +3274,8 @@ static int rescale_down_limbs(alch_ring* r, alch_ring* rout, char* cur, char* pi
         HIP_TRY(hipGetLastError());
         cur = nxt;
     }
-    if (dec_c0 && (rc = do_columns<W>(rout, GEN_L, out, per * first, now, per, r->stream)) != ALCH_OK) return rc;
-    if (!pow_out && (rc = do_crt<W>(rout, out, per * first, per * now, false, nullptr, r->stream)) != ALCH_OK) return rc;
+    if (dec_c0 && (rc = do_columns<W>(rout, GEN_L, out, per * first, now, per, r)) != ALCH_OK) return rc;
+    if (!pow_out && (rc = do_crt<W>(rout, out, per * first, per * now, false, nullptr, r)) != ALCH_OK) return rc;
     return ALCH_OK;
 }
 
@@ -3621,7 +3624,7 @@ static int do_tunnel(const alch_tunnel* t, alch_ring* rin, const void* in, void*
         // Pow basis of R' (a copy: the caller's ciphertexts are left alone); c0 onto relative-Dec (x) Pow(E')
         // Pow-basis input is read in place (c1 always; c0 through an out-of-place lInv into the scratch when the tunnel needs one)
         const bool pin = (flags & ALCH_POW_IN) != 0;
-        if (!pin && (rc = do_crt<W>(rin, win, 0, 2 * now, true, src, rs->stream)) != ALCH_OK) return rc;
+        if (!pin && (rc = do_crt<W>(rin, win, 0, 2 * now, true, src, rs)) != ALCH_OK) return rc;
         if (dec_c0) {
             GenCall<W> g{};
             g.op = GEN_LINV; g.ring = &dev_ring<W>(rin); g.gen = &gen_dev<W>(rin); g.stream = rs->stream;
@@ -3644,7 +3647,7 @@ static int do_tunnel(const alch_tunnel* t, alch_ring* rin, const void* in, void*
             g.op = GEN_CRT; g.ring = &dv; g.gen = &gv; g.stream = rs->stream;
             g.data = reinterpret_cast<W*>(x0); g.first_poly = 0; g.npoly = now * (size_t)D * Lx;
             if ((rc = launch(g, "tunnel crt")) != ALCH_OK) return rc;
-        } else if ((rc = do_crt<W>(rx, x0, 0, now * D, false, nullptr, rs->stream)) != ALCH_OK) return rc;
+        } else if ((rc = do_crt<W>(rx, x0, 0, now * D, false, nullptr, rs)) != ALCH_OK) return rc;
         W* po = reinterpret_cast<W*>(reinterpret_cast<char*>(out) + done * 2 * ebs);
         // k_tunnel_mac_e starts its accumulators from evalLin's constant term itself: no pass for it then
         const bool mac_e = sizeof(W) == 4 && !fused && (slot_e ? t->pieces_ok : true) && rs->n % 4 == 0 && rx->n % 4 == 0 && rs->opts.tunnel_mac;
@@ -3693,12 +3696,12 @@ static int do_tunnel(const alch_tunnel* t, alch_ring* rin, const void* in, void*
 
 // crt / crtInv in place of `count` elements that hold only the last L - u limbs of two-power ring r ([elem][L - u][n])
 template <typename W>
-static int crt_suffix(alch_ring* r, int u, void* data, size_t count, bool inverse, hipStream_t stream) {
-    if (u == 0) return do_crt<W>(r, data, 0, count, inverse, nullptr, stream);
+static int crt_suffix(alch_ring* r, int u, void* data, size_t count, bool inverse, const alch_ring* on) {
+    if (u == 0) return do_crt<W>(r, data, 0, count, inverse, nullptr, on);
     const DevRing<W> dv = suffix_view<W>(r, u);
     NttCall<W> c{};
     c.op = inverse ? OP_CRTINV : OP_CRT;
-    c.ring = &dv; c.stream = stream; c.data = reinterpret_cast<W*>(data);
+    c.ring = &dv; c.stream = on->stream; c.data = reinterpret_cast<W*>(data);
     c.first_poly = 0; c.npoly = count * (size_t)dv.L;
     return launch(r, c, "crt");
 }
@@ -3760,8 +3763,8 @@ static int do_tunnel_pow2(const alch_tunnel* t, alch_ring* rin, const void* in, 
         if (!pin) {
             if (split_ring(rin)) {                     // the split transforms work in place only
                 HIP_TRY(hipMemcpyAsync(win, src, now * 2 * ebr, hipMemcpyDeviceToDevice, rs->stream));
-                if ((rc = do_crt<W>(rin, win, 0, 2 * now, true, nullptr, rs->stream)) != ALCH_OK) return rc;
-            } else if ((rc = do_crt<W>(rin, win, 0, 2 * now, true, src, rs->stream)) != ALCH_OK) return rc;
+                if ((rc = do_crt<W>(rin, win, 0, 2 * now, true, nullptr, rs)) != ALCH_OK) return rc;
+            } else if ((rc = do_crt<W>(rin, win, 0, 2 * now, true, src, rs)) != ALCH_OK) return rc;
         }
         const W* pow_in = reinterpret_cast<const W*>(pin ? src : win);
         W* px0 = c0_in_place ? nullptr : reinterpret_cast<W*>(x0);
@@ -3769,7 +3772,7 @@ static int do_tunnel_pow2(const alch_tunnel* t, alch_ring* rin, const void* in, 
         else launch_tun2_gather<W, true>(rs, d, pow_in, px0, reinterpret_cast<W*>(dig), n_d, now, sm, scale, (u32)dup);
         HIP_TRY(hipGetLastError());
         // constant term: crt of the E'-coefficients of c0 (evalLin itself is the inner product's starting value)
-        if (px0 && (rc = crt_suffix<W>(rd, dup, x0, now * d, false, rs->stream)) != ALCH_OK) return rc;
+        if (px0 && (rc = crt_suffix<W>(rd, dup, x0, now * d, false, rs)) != ALCH_OK) return rc;
         // linear term: the digits' crt
         if (base2 && !split_ring(rd)) {                // decompose + reduce in the transforms' loader
             NttCall<W> nc{};
@@ -3789,7 +3792,7 @@ static int do_tunnel_pow2(const alch_tunnel* t, alch_ring* rin, const void* in, 
                     HIP_TRY(hipGetLastError());
                 }
             }
-            if ((rc = do_crt<W>(rd, dig, 0, now * d * GD, false, nullptr, rs->stream)) != ALCH_OK) return rc;
+            if ((rc = do_crt<W>(rd, dig, 0, now * d * GD, false, nullptr, rs)) != ALCH_OK) return rc;
         }
         W* po = reinterpret_cast<W*>(reinterpret_cast<char*>(out) + done * 2 * ebs);
         const size_t pieces = (now + 3) / 4 * (size_t)L * (rs->n / Vec4<W>::LANES);

@@ -144,7 +144,7 @@ extern "C" int alch_buf_embed(alch_buf* dst, const alch_buf* src, size_t count, 
         if ((rc = scratch_get(small, count, &s)) != ALCH_OK) return rc;
         BIND(big);
         HIP_TRY(hipMemcpyAsync(s->dptr, src->dptr, count * elem_bytes(small), hipMemcpyDeviceToDevice, big->stream));
-        if ((rc = columns(small, GEN_L, s->dptr, 0, count, 1, big->stream)) != ALCH_OK) return rc;
+        if ((rc = columns(small, GEN_L, s->dptr, 0, count, 1, big)) != ALCH_OK) return rc;
         from = s;
     }
     const int32_t* tab = basis == ALCH_BASIS_CRT ? t->slot_small : t->pow_gather;

@@ -136,7 +136,16 @@ int alch_modulus_units(uint64_t q);
  * oracle: psi (primitive m-th root), and the smallest generator. */
 int alch_host_root(uint32_t m, uint64_t q, uint64_t *psi, uint64_t *generator);
 int alch_ring_n(const alch_ring *ring, uint32_t *n, int *L, int *word_bytes);
-/* Use an externally created hipStream_t (e.g. torch's current stream) for all work of this ring. */
+/* Use an externally created hipStream_t (e.g. torch's current stream) for all work of this ring.
+ * Guarantee: the call first waits for everything the ring has queued on its previous stream, so no work is lost; from then on every
+ * kernel and copy of this ring's entry points -- including the ones another ring's call queues "as part of this ring's pipeline"
+ * (tunnel, modSwitch, mul_ across rings) -- is queued on `hip_stream` or on internal streams that fork from it and join it again
+ * before the call returns.  Work the caller queued on `hip_stream` before a call is therefore seen by the call, and work queued on
+ * it after the call sees the call's results; buffers of other rings are ordered against it with events exactly as for a stream the
+ * library created.  Every value of `hip_stream` names a stream: the null stream (0, what torch.cuda.current_stream() is
+ * unless the caller switched streams) is accepted and is used as such.  The stream stays the caller's: the library never destroys
+ * it (alch_ring_destroy waits for the work queued on it and destroys only the ring's internal streams), and the caller keeps it
+ * alive while the ring, or a ring that took it over through alch_ring_share_stream, still uses it. */
 int alch_ring_set_stream(alch_ring *ring, void *hip_stream);
 /* Launch-structure options of the fused hot-path kernels (results never depend on them; tests sweep them).  The
  * library reads no environment variable.  Names: "chunk" (ciphertexts per launch group, >= 8, default 1024),
