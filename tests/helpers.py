@@ -321,6 +321,20 @@ def threshold_moduli(rng, m, count):
     return rng.sample(sorted(q for q in pool if q < (1 << 31)), count)
 
 
+def word32_edge_rings(m):
+    """Two-limb rings of primes = 1 (mod m) at the dispatch boundaries of the 4-byte two-power kernels: the first primes above 2^30
+    (the smallest ring that is not q30), one limb on each side of 2^30, and for the largest prime below 2^31 and below 2^30 the
+    partner just above and just at or below (qmax - 1) / 2 (balanced / not).  The rings of tests/test_gpu_word32_edges.py for
+    m = 2^16; the modulus class the sweeps draw from."""
+    top30, above30 = primes_below(m, 1, 1 << 30)[0], primes_1_mod(m, 2, 1 << 30)
+    out = {"above30": above30, "straddle30": [top30, above30[0]]}
+    for bits, qmax in ((31, primes_below(m, 1, 1 << 31)[0]), (30, top30)):
+        half = (qmax - 1) // 2
+        out[f"edge_bal{bits}"] = [qmax, primes_1_mod(m, 1, half)[0]]
+        out[f"edge_unbal{bits}"] = [qmax, primes_below(m, 1, half + 1)[0]]
+    return out
+
+
 def tunnel_worst_operands(oracle_lib, rp, sp, qs, batch, plus, check_digits):
     """The worst case of a tunnel's hint inner product on 32-bit words, as operands(rng, d_rel, D, n_r, n_s) -> (lin, ks, cts) (D: digits
     per E'-coefficient; the kernel sums d_rel D products per slot).  lin, c0 and the odd ciphertexts: extreme words.  Hint rows:

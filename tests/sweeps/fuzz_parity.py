@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Randomised parity sweep on the GPU box: alch_ct_mul_relin and alch_ct_mul_full on two-power rings of random size, limb count, moduli
-class (31-bit, below 2^30, just below 2^62 on 8-byte words), operand class (uniform words, or the extreme residues of helpers.extreme_words), gadget (TrivGad; BaseBGad 2 at small sizes, hint at, above or below the operands' limb count), batch and launch options, every result word compared with the C restatement (oracle/ is the checker, as in
+class (31-bit, below 2^30, the two-limb rings around 2^30 and either side of the balanced / unbalanced boundary of helpers.word32_edge_rings, just below 2^62 on 8-byte words), operand class (uniform words, or the extreme residues of helpers.extreme_words), gadget (TrivGad; BaseBGad 2 at small sizes, hint at, above or below the operands' limb count), batch and launch options, every result word compared with the C restatement (oracle/ is the checker, as in
 tests/).  usage: tests/sweeps/fuzz_parity.py [seconds] [seed]   -- prints one line per case class and a final tally; exits non-zero on a mismatch."""
 import os, random, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -9,11 +9,12 @@ import numpy as np
 import alchemy_amd as A
 from alchemy_amd import capi
 from oracle import cref
-from helpers import extreme_words, oracle_full_mul, oracle_full_mul_base2_down, oracle_mul_relin_base2, primes_below
+from helpers import extreme_words, oracle_full_mul, oracle_full_mul_base2_down, oracle_mul_relin_base2, primes_below, word32_edge_rings
 
 SIX31 = [2147352577, 2146959361, 2146041857, 2144468993, 2142502913, 2135818241]          # = 1 mod 2^17
 SIX30 = [1073479681, 1071513601, 1070727169, 1068236801, 1065484289, 1064697857]          # = 1 mod 2^17, below 2^30
 SIX62 = primes_below(1 << 16, 6, 1 << 62)                                                 # = 1 mod 2^16, the top of the accepted range
+EDGE32 = word32_edge_rings(1 << 17)                                                       # = 1 mod 2^17: the 4-byte dispatch boundaries (q30, balanced)
 OPTS = {"chunk": [8, 16, 24], "one_stream": [0, 1], "pipe": [0, 1], "nstreams": [1, 2, 3, 4], "ks_map": [0, 1], "ks_rev": [0, 1],
         "q30": [0, 1], "split_fused": [0, 1, 2], "ks_grid": [8, 24, 4096], "ti_split": [0, 1, 5], "crt_half": [0, 1]}
 
@@ -28,10 +29,15 @@ def main():
     while time.time() - t0 < budget:
         logn = rng.choice([4, 6, 8, 10, 11, 11, 12, 13, 14, 15, 15, 15, 16])
         n = 1 << logn
-        pool = rng.choice([SIX31, SIX30, SIX62])
+        pool = rng.choice([SIX31, SIX30, SIX62, EDGE32])
         if pool is SIX62 and logn > 15: logn, n = 15, 1 << 15          # 8-byte words: n <= 2^15
         L = rng.randint(1, 6)
-        qs = rng.sample(pool, L) if rng.random() < 0.5 else pool[:L]
+        edge = None
+        if pool is EDGE32:                                             # an edge pair, half the time behind one more limb (so that the full mul_ applies)
+            edge = rng.choice(sorted(EDGE32))
+            qs = ([rng.choice(SIX30[1:] if max(EDGE32[edge]) < 1 << 30 else SIX31[1:])] if rng.random() < 0.5 else []) + EDGE32[edge]
+            L = len(qs)
+        else: qs = rng.sample(pool, L) if rng.random() < 0.5 else pool[:L]
         batch = rng.randint(1, 40 if logn <= 13 else (12 if logn <= 14 else 5))
         if logn >= 15 and rng.random() < 0.25: batch = rng.randint(9, 30)          # several chunks of 8 .. 24 at the fused kernels' sizes
         opts = {k: rng.choice(v) for k, v in OPTS.items() if rng.random() < 0.4}
@@ -40,7 +46,7 @@ def main():
         if extreme: rnd = lambda c, q_: extreme_words(nprng, c, n, q_)
         else: rnd = lambda c, q_: np.stack([np.stack([nprng.integers(0, q, size=n, dtype=np.int64) for q in q_], axis=1) for _ in range(c)])
         s_pre = None if rng.random() < 0.5 else [q - 1 for q in qs] if extreme else [rng.randrange(1, q) for q in qs]
-        key = ("full" if full else "relin", logn, ("q30" if pool is SIX30 else "q62" if pool is SIX62 else "q31") + ("_extreme" if extreme else ""))
+        key = ("full" if full else "relin", logn, (edge if edge else "q30" if pool is SIX30 else "q62" if pool is SIX62 else "q31") + ("_extreme" if extreme else ""))
         if logn <= 11 and L <= 3 and rng.random() < 0.25:              # BaseBGad 2 hints (small sizes: 30 digits per limb)
             batch = min(batch, 4)
             kind = rng.choice(["relin", "full_up", "full_down"]) if L >= 2 else "relin"

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Randomised sweep of mul_ one SHE operation at a time against the fused entry points: random ring (two-power 32 .. 2^16, or
-m = 2^a 3^b 5^c 7^d 13^e with phi(m) <= 3000), 30-bit moduli, or 59-bit or just below 2^62 on two-power rings, 2..5 limbs, TrivGad or BaseBGad 2, random
+m = 2^a 3^b 5^c 7^d 13^e with phi(m) <= 3000), 30-bit moduli, or 59-bit or just below 2^62 on two-power rings, or (two-power rings) an edge pair of helpers.word32_edge_rings -- around 2^30, either side of the balanced / unbalanced boundary -- behind the largest primes below its qmax, 2..5 limbs, TrivGad or BaseBGad 2, random
 launch options (split_fused, gen_fused, rs_lin, scratch_mib), batch 1..9, with and without s_pre.  Per case, on uniform words or on the
 extreme residues of helpers.extreme_words (s_pre = -1 then):
   key_switch_quad(mul(a, b, s))                              == alch_ct_mul_relin(a, b, s)          (s also split between the calls)
@@ -16,7 +16,7 @@ import numpy as np
 import alchemy_amd as A
 from alchemy_amd import capi
 from alchemy_amd import mulsteps as MS
-from helpers import extreme_words, primes_1_mod, primes_below
+from helpers import extreme_words, primes_1_mod, primes_below, word32_edge_rings
 
 TRIV, BASE2, PIN, POUT = capi.ALCH_GAD_TRIV, capi.ALCH_GAD_BASE2, capi.ALCH_POW_IN, capi.ALCH_POW_OUT
 
@@ -64,6 +64,11 @@ def main():
         gadget = BASE2 if (n <= 4096 and rng.random() < 0.4) else TRIV
         top = wide and rng.random() < 0.5                              # the top of the accepted range instead of its middle
         qs = primes_below(m, L, 1 << 62) if top else primes_1_mod(m, L, lo=(1 << 58) if wide else rng.choice([1 << 28, 1 << 29]))
+        edge = None
+        if pow2 and not wide and rng.random() < 0.3:                   # the 4-byte dispatch boundaries: q30 or not, balanced or not
+            pairs = word32_edge_rings(m)
+            edge = rng.choice(sorted(pairs))
+            qs = [q for q in primes_below(m, L, max(pairs[edge])) if q not in pairs[edge]][:L - 2] + pairs[edge]
         extreme = rng.random() < 0.3
         batch = rng.randint(1, 3 if n >= 1 << 14 else 9)
         rings = [A.Ring(m, qs[L - k:]) for k in range(1, L + 1)]
@@ -72,7 +77,7 @@ def main():
         if rng.random() < 0.5: opts["gen_fused"] = rng.choice([0, 1])
         if rng.random() < 0.5: opts["rs_lin"] = rng.choice([0, 1])
         if rng.random() < 0.5: opts["scratch_mib"] = rng.choice([1, 2, 64])
-        info = dict(m=m, qs=qs, gadget=gadget, batch=batch, opts=opts, extreme=extreme, seed=seed)
+        info = dict(m=m, qs=qs, edge=edge, gadget=gadget, batch=batch, opts=opts, extreme=extreme, seed=seed)
         ring = rings[-1]
         s = None if rng.random() < 0.3 else [q - 1 for q in qs] if extreme else [rng.randrange(1, q) for q in qs]
         a, b = operands(ring, 2 * batch, rng.randrange(1 << 30), extreme), operands(ring, 2 * batch, rng.randrange(1 << 30), extreme)
@@ -123,7 +128,7 @@ def main():
         if (a.checksum(), b.checksum()) != sums:
             print("INPUT MODIFIED", info); return 1
         cases += 1
-        key = ("two-power" if pow2 else "general", "62-bit" if top else "60-bit" if wide else "32-bit", "BaseBGad2" if gadget == BASE2 else "TrivGad",
+        key = ("two-power" if pow2 else "general", "62-bit" if top else "60-bit" if wide else edge if edge else "32-bit", "BaseBGad2" if gadget == BASE2 else "TrivGad",
                "extreme" if extreme else "uniform")
         tally[key] = tally.get(key, 0) + 1
         if cases % 25 == 0: print(f"{cases} cases, {time.time() - t0:.0f} s", flush=True)
