@@ -138,6 +138,10 @@ def crt_def(a: Sequence[int], idx: Index, q: int) -> List[int]:
     """slot s = sum_j a_j omega_m^(u(s) e(j)): direct evaluation over the whole index (O(n^2), numpy rows)."""
     n, m = idx.n, idx.m
     w = omega_m(q, m)
+    if q >= 1 << 32:                                     # a product of two residues leaves uint64: Python integers
+        pw = [pow(w, t, q) for t in range(m)]
+        exs, al = [idx.pow_exponent(j) for j in range(n)], [x % q for x in a]
+        return [sum(pw[e * u % m] * x for e, x in zip(exs, al)) % q for u in (idx.slot_unit(s) for s in range(n))]
     powers = np.empty(m, dtype=np.uint64)
     acc = 1
     for t in range(m):

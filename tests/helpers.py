@@ -335,6 +335,51 @@ def word32_edge_rings(m):
     return out
 
 
+def resident_edge_rings(m):
+    """The nine rings of tests/test_gpu_resident_edges.py for primes = 1 (mod m): the two largest primes below 2^31 and below 2^62, the
+    first two above 2^31 (the smallest that take 8-byte words), the largest 31-bit / 62-bit prime next to a 17-bit one and a 21-bit /
+    32-bit one, and for either top prime the partner just above and just below (qmax - 1) / 2 (balanced / not; the 62-bit pair by the
+    rule of tests/test_gpu_word64_edges.py).  The modulus class the resident-batch sweeps draw from."""
+    e32 = word32_edge_rings(m)
+    top31, top62, low64 = primes_below(m, 2, 1 << 31), primes_below(m, 2, 1 << 62), primes_1_mod(m, 2, 1 << 31)
+    q17, half = primes_1_mod(m, 1, 1 << 16)[0], (top62[0] - 1) // 2
+    return {"TOP31": top31, "MIX31": [top31[0], q17, primes_1_mod(m, 1, 1 << 20)[0]],
+            "EDGE_BAL31": e32["edge_bal31"], "EDGE_UNBAL31": e32["edge_unbal31"],
+            "LOW64": low64, "TOP62": top62, "MIX64": [top62[0], q17, low64[0]],
+            "EDGE_BAL62": [top62[0], primes_1_mod(m, 1, half)[0]], "EDGE_UNBAL62": [top62[0], primes_below(m, 1, half)[0]]}
+
+
+RESIDENT_WORD_BYTES = {"TOP31": 4, "MIX31": 4, "EDGE_BAL31": 4, "EDGE_UNBAL31": 4, "LOW64": 8, "TOP62": 8, "MIX64": 8, "EDGE_BAL62": 8,
+                       "EDGE_UNBAL62": 8}
+
+
+def draw_resident_edge_ring(rnd, m):
+    """("edge:NAME", moduli): one of resident_edge_rings(m) at random -- the draw of the ext, encrypt and hint sweeps (rnd: random.Random)."""
+    name = rnd.choice(sorted(RESIDENT_WORD_BYTES))
+    return "edge:" + name, resident_edge_rings(m)[name]
+
+
+def check_resident_edge_rings(rings):
+    """What the cases of tests/test_gpu_resident_edges.py need of resident_edge_rings(m), on the moduli alone: the word size every ring
+    must get, (qmax - 1) / 2 < qmin exactly on the BAL rings, q_i < 2 q_j for all i, j (LiftPar::bal) on exactly the same, the TOP primes
+    within 2^22 of their power of two, the small limbs of 17, 21 and 32 bits."""
+    assert set(rings) == set(RESIDENT_WORD_BYTES)
+    for name, qs in rings.items():
+        assert len(set(qs)) == len(qs) and (8 if max(qs) >= (1 << 31) else 4) == RESIDENT_WORD_BYTES[name], name
+        assert max(qs) < ((1 << 31) if RESIDENT_WORD_BYTES[name] == 4 else (1 << 62)), name
+        balanced = (max(qs) - 1) // 2 < min(qs)
+        assert balanced == (not name.startswith(("EDGE_UNBAL", "MIX"))), name
+        assert all(2 * a > b for a in qs for b in qs) == balanced, name
+    assert all((1 << 31) - (1 << 22) < q < (1 << 31) for q in rings["TOP31"])
+    assert all((1 << 62) - (1 << 22) < q < (1 << 62) for q in rings["TOP62"])
+    assert all((1 << 31) < q < (1 << 31) + (1 << 22) for q in rings["LOW64"])
+    assert [(q - 1).bit_length() for q in rings["MIX31"]] == [31, 17, 21] and [(q - 1).bit_length() for q in rings["MIX64"]] == [62, 17, 32]
+    for bits in (31, 62):
+        bal, unbal = rings[f"EDGE_BAL{bits}"], rings[f"EDGE_UNBAL{bits}"]
+        top = rings[f"TOP{bits}"][0]
+        assert bal[0] == unbal[0] == top and unbal[1] <= (top - 1) // 2 < bal[1] and bal[1] - unbal[1] < 1 << (22 if bits == 31 else 32)
+
+
 def tunnel_worst_operands(oracle_lib, rp, sp, qs, batch, plus, check_digits):
     """The worst case of a tunnel's hint inner product on 32-bit words, as operands(rng, d_rel, D, n_r, n_s) -> (lin, ks, cts) (D: digits
     per E'-coefficient; the kernel sums d_rel D products per slot).  lin, c0 and the odd ciphertexts: extreme words.  Hint rows:

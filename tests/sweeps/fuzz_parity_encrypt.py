@@ -18,7 +18,7 @@ import torch  # noqa: F401,E402  (one HIP runtime per process: before the librar
 import alchemy_amd as A  # noqa: E402
 import gauss_model as GM  # noqa: E402
 from alchemy_amd import encrypt as E  # noqa: E402
-from helpers import primes_1_mod, primes_below  # noqa: E402
+from helpers import draw_resident_edge_ring, primes_1_mod, primes_below  # noqa: E402
 
 INDICES = [4, 8, 16, 32, 64, 256, 3, 7, 9, 13, 21, 27, 45, 60, 63, 91, 169, 420, 1365, 4095, 2912]
 P_SET = [None, 2, 3, 7, 8, 32, 1 << 20, (1 << 31) - 1]
@@ -44,7 +44,8 @@ def main():
     with open(os.path.join(ROOT, "profiles", "fuzz_parity_encrypt.log"), "w") as log:
         for trial in range(a.trials):
             m, L, p = rnd.choice(INDICES), rnd.randint(1, 4), rnd.choice(P_SET)
-            kind, qs = moduli(rnd, m, L)
+            kind, qs = draw_resident_edge_ring(rnd, m) if rnd.random() < 0.25 else moduli(rnd, m, L)      # one trial in four: the edge rings
+            L = len(qs)
             count, first = rnd.randint(1, 9), rnd.randint(0, 3)
             seed, elem0 = rnd.getrandbits(64), rnd.choice([0, rnd.getrandbits(20), (1 << 64) - rnd.randint(1, 5)])
             svar = rnd.choice([3.0, 5.0, 50.0]) / math.sqrt(GM.totient(m)) * (float(p) ** 2 if p else 1.0)

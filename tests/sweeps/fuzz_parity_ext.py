@@ -9,7 +9,7 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import alchemy_amd as A
 from oracle import model_gen as G
-from helpers import primes_1_mod
+from helpers import draw_resident_edge_ring, primes_1_mod
 
 limbs = lambda arr: np.asarray(arr).T.tolist()
 
@@ -34,6 +34,7 @@ def main():
         s = G.Index(m)
         qs = primes_1_mod(mb, 2, lo=rng.choice([1 << 20, 1 << 29, 1 << 30]))
         if max(qs) >= 1 << 31: continue
+        if rng.random() < 0.25: qs = draw_resident_edge_ring(rng, mb)[1]          # one pair in four: the edge rings, 8-byte words included
         rs, rb = A.Ring(m, qs), A.Ring(mb, qs)
         x = np.stack([nprng.integers(0, q, size=s.n, dtype=np.int64) for q in qs], axis=1)
         y = np.stack([nprng.integers(0, q, size=b.n, dtype=np.int64) for q in qs], axis=1)

@@ -18,7 +18,7 @@ import alchemy_amd as A  # noqa: E402
 import gauss_model as GM  # noqa: E402
 from alchemy_amd import capi  # noqa: E402
 from alchemy_amd import hints as H  # noqa: E402
-from helpers import primes_1_mod, primes_below  # noqa: E402
+from helpers import draw_resident_edge_ring, primes_1_mod, primes_below  # noqa: E402
 
 INDICES = [4, 8, 16, 32, 64, 256, 3, 7, 9, 13, 21, 27, 45, 60, 63, 91, 169, 420]
 M64 = (1 << 64) - 1
@@ -56,7 +56,8 @@ def main():
     with open(os.path.join(ROOT, "profiles", "fuzz_parity_hints.log"), "w") as log:
         for trial in range(a.trials):
             m, L = rnd.choice(INDICES), rnd.randint(1, 4)
-            kind, qs = moduli(rnd, m, L)
+            kind, qs = draw_resident_edge_ring(rnd, m) if rnd.random() < 0.25 else moduli(rnd, m, L)      # one trial in four: the edge rings
+            L = len(qs)
             gadget = rnd.choice([capi.ALCH_GAD_TRIV, capi.ALCH_GAD_BASE2])
             ring = A.Ring(m, qs)
             n, D = ring.n, ring.gadget_digits(gadget)

@@ -15,13 +15,13 @@ import pytest
 import alchemy_amd as A
 from alchemy_amd import capi
 from alchemy_amd import decrypt as D
-from helpers import assert_reduced, extreme_words, primes_1_mod, primes_below, to_aos
+from helpers import assert_reduced, extreme_words, primes_1_mod, primes_below, to_aos, word32_edge_rings
 from test_gpu_word64_edges import EDGE_BAL, EDGE_UNBAL
 
 pytestmark = pytest.mark.gpu
 
 P_SET = [2, 8, 7, 1 << 30]
-P_MAX = (1 << 31) - 1                            # the largest destination modulus alch_buf_lift accepts; run by the 62-bit rows
+P_MAX = (1 << 31) - 1                            # the largest destination modulus alch_buf_lift accepts; run by the 62- and 31-bit rows
 
 
 def to_digits(x, qs):
@@ -97,16 +97,34 @@ def lift_ring_cases():
         cases.append((m, L, 62, False))
     cases.append((64, 2, 62, "edge_bal"))       # either side of the boundary q_i < 2 q_j that sets LiftPar::bal
     cases.append((64, 2, 62, "edge_unbal"))
+    cases.append((32, 4, 31, True))             # the largest primes below 2^31: k_lift<u32> at the top of its range, bal 1 and 0
+    cases.append((32, 4, 31, False))
+    cases.append((420, 2, 31, True))
+    cases.append((512, 2, 31, True))
+    cases.append((64, 2, 31, "edge_bal31"))     # the same boundary on 4-byte words
+    cases.append((64, 2, 31, "edge_unbal31"))
+    cases.append((64, 2, 32, "low64"))          # the first primes above 2^31: the smallest ring that runs k_lift<u64>
     return cases
 
 
 def moduli(m, L, bits, balanced):
-    """bits < 62: the first primes above 2^(bits-1); bits = 62: the last ones BELOW 2^62 (nothing at or above it is accepted)."""
+    """bits < 62: the first primes above 2^(bits-1); bits = 62: the last ones BELOW 2^62 (nothing at or above it is accepted); bits =
+    31: the last ones below 2^31 (the top of the 4-byte words).  Tags: the rings either side of q_i < 2 q_j on 8-byte words (edge_bal,
+    edge_unbal) and on 4-byte words (edge_bal31, edge_unbal31: helpers.word32_edge_rings), and the first two primes above 2^31 (low64)."""
     if balanced in ("edge_bal", "edge_unbal"):
         qs = EDGE_BAL if balanced == "edge_bal" else EDGE_UNBAL
         assert all(2 * a > b for a in qs for b in qs) == (balanced == "edge_bal")
         return qs
-    big = (lambda count: primes_below(m, count, 1 << 62)) if bits == 62 else (lambda count: primes_1_mod(m, count, 1 << (bits - 1)))
+    if balanced in ("edge_bal31", "edge_unbal31"):
+        qs = word32_edge_rings(m)[balanced]
+        assert len(qs) == L and max(qs) < (1 << 31) and all(2 * a > b for a in qs for b in qs) == (balanced == "edge_bal31")
+        return qs
+    if balanced == "low64":
+        qs = primes_1_mod(m, L, 1 << 31)
+        assert bits == 32 and all((1 << 31) < q < (1 << 31) + (1 << 22) for q in qs)
+        return qs
+    big = ((lambda count: primes_below(m, count, 1 << bits)) if bits in (31, 62)
+           else (lambda count: primes_1_mod(m, count, 1 << (bits - 1))))
     if balanced:
         return big(L)
     lo = primes_1_mod(m, L - 1, 0)                                     # the smallest primes that are 1 mod m
@@ -130,7 +148,7 @@ def test_lift_crafted(m, L, bits, balanced):
     want_digits = [to_digits(max(abs(v) for v in x), qs) for x in lifted]
     assert all(d == to_digits((cr.Q - 1) // 2, qs) for d in want_digits)
     lifted_np = np.array(lifted, dtype=object)
-    for p in P_SET + ([P_MAX] if bits == 62 else []):
+    for p in P_SET + ([P_MAX] if bits in (31, 62) else []):
         zp = A.Ring(m, [p], nocrt=True)
         dst = zp.alloc(total + 3)
         for l in (1, p - 1):
@@ -161,7 +179,8 @@ def test_lift_crafted(m, L, bits, balanced):
 
 @pytest.mark.parametrize("m,L,bits,balanced", [(32, 3, 30, True), (420, 2, 30, True), (1 << 13, 3, 30, True), (1 << 13, 8, 30, True),
                                                (1 << 12, 3, 59, True), (32, 4, 30, False), (512, 2, 30, True),
-                                               (1 << 12, 3, 62, True), (32, 4, 62, False), (64, 2, 62, "edge_bal"), (64, 2, 62, "edge_unbal")])
+                                               (1 << 12, 3, 62, True), (32, 4, 62, False), (64, 2, 62, "edge_bal"), (64, 2, 62, "edge_unbal"),
+                                               (64, 2, 31, "edge_bal31"), (64, 2, 31, "edge_unbal31"), (64, 2, 32, "low64")])
 def test_lift_maximum_position_and_sign(m, L, bits, balanced):
     """The lexicographic maximum of |x|: small random elements with ONE planted magnitude M = Q // 3 + 5 at index 0, at n - 1, at
     n - 3 (a lane of the last wave), as -M, as +M and -M together, as +M against -(M + 1) (the negative wins by one: complement and
@@ -209,20 +228,21 @@ def oracle_error_term(O, general, comps, sk, s_pre):
 
 
 ERROR_TERM_RINGS = [(32, 2, 30, 3), (64, 3, 30, 3), (45, 3, 30, 3), (420, 2, 30, 3), (11648, 5, 30, 2), (1 << 12, 2, 60, 3), (1 << 17, 2, 30, 2),
-                    (1 << 12, 2, 62, 3), (420, 2, 62, 3)]               # 62: just below 2^62, on extreme words
+                    (1 << 12, 2, 62, 3), (420, 2, 62, 3),               # 62: just below 2^62, on extreme words
+                    (1 << 12, 2, 31, 3), (420, 2, 31, 3)]               # 31: just below 2^31 (k_ct_eval_sk<u32>), on extreme words
 
 
 @pytest.mark.parametrize("m,L,bits,batch", ERROR_TERM_RINGS)
 def test_error_term_matches_the_oracle(oracle_lib, m, L, bits, batch):
     """alch_ct_error_term on random ciphertext words (parity does not need them valid): degree 1 and 2, with and without s_pre, CRT
     input and ALCH_POW_IN, written at an element offset of the output; equal to lInv(crtInv(Horner)) limb by limb; input untouched.
-    The 62-bit rows draw key, ciphertexts and scalar from the extreme residues (helpers.extreme_words, s_pre = -1)."""
+    The 62-bit and the 31-bit rows draw key, ciphertexts and scalar from the extreme residues (helpers.extreme_words, s_pre = -1)."""
     qs = moduli(m, L, bits, True)
     ring = A.Ring(m, qs)
     assert ring.word_bytes == (4 if bits <= 31 else 8)
     O, general = oracle_ring(oracle_lib, m, qs)
     rng = np.random.default_rng(m + L)
-    words = extreme_words if bits == 62 else rand_elems
+    words = extreme_words if bits in (31, 62) else rand_elems
     sk = words(rng, 2, ring.n, qs)
     gsk = ring.upload(sk)
     for degree in (1, 2):
@@ -230,7 +250,7 @@ def test_error_term_matches_the_oracle(oracle_lib, m, L, bits, batch):
         cts = words(rng, per * batch, ring.n, qs)
         for with_s_pre in (False, True):
             s_pre = [int(rng.integers(1, q)) for q in qs] if with_s_pre else None
-            if with_s_pre and bits == 62:
+            if with_s_pre and bits in (31, 62):
                 s_pre = [q - 1 for q in qs]
             want = [oracle_error_term(O, general, [cts[per * b + c] for c in range(per)], sk[1], s_pre) for b in range(batch)]
             for flags in (0, capi.ALCH_POW_IN):
@@ -249,14 +269,10 @@ def test_error_term_matches_the_oracle(oracle_lib, m, L, bits, batch):
                 del out, gin
 
 
-@pytest.mark.parametrize("m,L,balanced", [(1 << 12, 3, True), (32, 4, False), (64, 2, "edge_bal"), (64, 2, "edge_unbal")])
-def test_decrypt_lift_moduli_below_2_62(oracle_lib, m, L, balanced):
-    """alch_ct_decrypt_lift (k_ct_eval_sk<u64>, then k_lift<u64> with bal 1 and 0) on extreme words, s_pre = -1, at the top of the
-    accepted modulus range: residues modulo 2^31 - 1 (the largest destination modulus) and modulo 8 and the digit vectors of max |x|
-    against the oracle's c(s) lifted in Python integers."""
-    qs = moduli(m, L, 62, balanced)
+def decrypt_lift_case(oracle_lib, m, L, bits, balanced, word_bytes):
+    qs = moduli(m, L, bits, balanced)
     ring = A.Ring(m, qs)
-    assert ring.word_bytes == 8
+    assert ring.word_bytes == word_bytes
     O, general = oracle_ring(oracle_lib, m, qs)
     n, batch, Q = ring.n, 3, prod(qs)
     rng = np.random.default_rng(62 + m + L)
@@ -279,6 +295,21 @@ def test_decrypt_lift_moduli_below_2_62(oracle_lib, m, L, balanced):
             assert digits[b] == to_digits(max(abs(v) for v in lifted[b]), qs), (p, b)
         del dst
     assert np.array_equal(gin.download(), cts)
+
+
+@pytest.mark.parametrize("m,L,balanced", [(1 << 12, 3, True), (32, 4, False), (64, 2, "edge_bal"), (64, 2, "edge_unbal")])
+def test_decrypt_lift_moduli_below_2_62(oracle_lib, m, L, balanced):
+    """alch_ct_decrypt_lift (k_ct_eval_sk<u64>, then k_lift<u64> with bal 1 and 0) on extreme words, s_pre = -1, at the top of the
+    accepted modulus range: residues modulo 2^31 - 1 (the largest destination modulus) and modulo 8 and the digit vectors of max |x|
+    against the oracle's c(s) lifted in Python integers."""
+    decrypt_lift_case(oracle_lib, m, L, 62, balanced, 8)
+
+
+@pytest.mark.parametrize("m,L,balanced", [(1 << 12, 3, True), (32, 4, False), (64, 2, "edge_bal31"), (64, 2, "edge_unbal31")])
+def test_decrypt_lift_moduli_below_2_31(oracle_lib, m, L, balanced):
+    """The 4-byte twin: k_ct_eval_sk<u32>, then k_lift<u32> with bal 1 and 0, on the largest primes below 2^31 and on the two rings
+    either side of q_i < 2 q_j."""
+    decrypt_lift_case(oracle_lib, m, L, 31, balanced, 4)
 
 
 # ---- semantic cases ----------------------------------------------------------------------------------------------------------------

@@ -23,13 +23,18 @@ def oracle_ring(m, qs):
     return cref.Ring(m // 2, qs) if m & (m - 1) == 0 else cref.GenRing(m, qs)
 
 
-def check_ct_encrypt(m, qs, B):
+def check_ct_encrypt(m, qs, B, words=None, word_bytes=None):
     """B ciphertexts from error terms at err_first = 1 and the key element 1; then the last B - B // 2 of them once more through a view
-    of another buffer with ct0 advanced."""
+    of another buffer with ct0 advanced.  words(rng, count, n, qs): the error terms and the key (default: alch_buf_fill_uniform)."""
     ring, orc = A.Ring(m, qs), oracle_ring(m, qs)
+    assert word_bytes is None or ring.word_bytes == word_bytes
     err, sk, out, uni = ring.alloc(B + 1), ring.alloc(2), ring.alloc(2 * B), ring.alloc(2 * B)
     err.fill_uniform(11)
     sk.fill_uniform(12)
+    if words is not None:
+        rng = np.random.default_rng(m + B)
+        err.upload(words(rng, B + 1, ring.n, qs))
+        sk.upload(words(rng, 2, ring.n, qs))
     seed = 0xC1C1 + m
     uni.fill_uniform(seed)
     E.ct_encrypt(out, B, err, sk, seed, err_first=1, sk_index=1)
@@ -45,6 +50,7 @@ def check_ct_encrypt(m, qs, B):
     E.ct_encrypt(other.view(2 * skip, 2 * (B - skip)), B - skip, err, sk, seed, err_first=1 + skip, sk_index=1, ct0=skip)
     again = other.download()
     assert np.array_equal(again[2 * skip:], got[2 * skip:]) and np.array_equal(again[:2 * skip], keep[:2 * skip])
+    return seed, got, u, e, s
 
 
 @pytest.mark.parametrize("word", [32, 64])

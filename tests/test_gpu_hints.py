@@ -55,16 +55,32 @@ def same(got, want):
 @pytest.mark.parametrize("m", [16, 64, 21, 45])
 def test_ct_ks_hint_equals_python_integers(m, word, gadget):
     qs = primes_1_mod(m, 2, 1 << 29) if word == 32 else primes_below(m, 2, 1 << 62)
-    ring = A.Ring(m, qs)
-    D = ring.gadget_digits(gadget)
-    assert D == len(gadget_entries(qs, gadget))
+    D = check_ks_hint(m, qs, gadget)
     if (m, word, gadget) == (45, 64, BASE2):
         assert D == 124
+
+
+def upload_words(words, seed, bufs, qs):
+    """Replace what fill_uniform wrote: words(rng, count, n, qs) for every buffer of bufs."""
+    rng = np.random.default_rng(seed)
+    for b in bufs:
+        b.upload(words(rng, b.n_elems, b.ring.n, qs))
+
+
+def check_ks_hint(m, qs, gadget, words=None, word_bytes=None):
+    """alch_ct_ks_hint with n_v = 2 and a nonzero offset on every buffer against expected_pairs; returns the digit count D.
+    words(rng, count, n, qs): the values, error terms and key (default: alch_buf_fill_uniform)."""
+    ring = A.Ring(m, qs)
+    assert word_bytes is None or ring.word_bytes == word_bytes
+    D = ring.gadget_digits(gadget)
+    assert D == len(gadget_entries(qs, gadget))
     n_v, out_first, v_first, err_first, sk_index, ct0, seed = 2, 3, 1, 2, 1, 3, 0xA5A5 + m
     total = n_v * D
     out, v, err, sk = ring.alloc(out_first + 2 * total), ring.alloc(v_first + n_v), ring.alloc(err_first + total), ring.alloc(2)
     uni = ring.alloc(2 * (ct0 + total))
     out.fill_uniform(1); v.fill_uniform(2); err.fill_uniform(3); sk.fill_uniform(4); uni.fill_uniform(seed)
+    if words is not None:
+        upload_words(words, m + gadget, (v, err, sk), qs)
     keep = out.download(0, out_first)
     H.ct_ks_hint(out, gadget, n_v, v, err, sk, seed, out_first=out_first, v_first=v_first, err_first=err_first, sk_index=sk_index, ct0=ct0)
     got, u = out.download(), uni.download()
@@ -75,9 +91,10 @@ def test_ct_ks_hint_equals_python_integers(m, word, gadget):
     for e, (b, a) in enumerate(want):
         assert same(got[out_first + 2 * e + 1], a), (m, e)
         assert same(got[out_first + 2 * e], b), (m, e)
+    return D
 
 
-def check_cut(m, qs, gadget, n_v, cut):
+def check_cut(m, qs, gadget, n_v, cut, words=None):
     """One call against two parts cut at entry `cut`, with ct0 advanced, in another buffer behind an offset."""
     ring = A.Ring(m, qs)
     D = ring.gadget_digits(gadget)
@@ -85,6 +102,8 @@ def check_cut(m, qs, gadget, n_v, cut):
     assert 0 < cut < total
     whole, parts, v, err, sk = ring.alloc(2 * total), ring.alloc(1 + 2 * total), ring.alloc(n_v), ring.alloc(total), ring.alloc(1)
     v.fill_uniform(5); err.fill_uniform(6); sk.fill_uniform(7); parts.fill_uniform(8)
+    if words is not None:
+        upload_words(words, m + cut, (v, err, sk), qs)
     H.ct_ks_hint(whole, gadget, n_v, v, err, sk, seed, ct0=ct0)
     H.ct_ks_hint_part(parts, gadget, 0, cut, v, err, sk, seed, out_first=1, ct0=ct0)
     H.ct_ks_hint_part(parts, gadget, cut, total - cut, v, err, sk, seed, out_first=1 + 2 * cut, err_first=cut, ct0=ct0 + cut)

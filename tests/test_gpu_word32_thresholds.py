@@ -2,7 +2,8 @@
 
 Inner products (k_tun2_mac<u32>, k_tunnel_mac_e and the composed general-index path, k_pt_mac<u32>): K = lazy_group(q) products are
 summed in 64 bits between two Montgomery reductions, K = min(8, floor((2^32 - 1) / q) - 2), none below K = 2.  Every class
-kmax = floor((2^32 - 1) / q) = 3 .. 11 (K = 0, 2, 3, 4, 5, 6, 7, 8, 8) runs here on the largest primes of the class -- the least
+kmax = floor((2^32 - 1) / q) = 2 .. 11 (K = 0, 0, 2, 3, 4, 5, 6, 7, 8, 8; class 2 reaches up to 2^31 and holds the reference's own
+moduli; the BaseBGad 2 and per-limb cases start at class 3) runs here on the largest primes of the class -- the least
 headroom under (K + 2) q < 2^32 -- and, in the tunnels, on the smallest ones too (R mod q is largest there, and with it the
 carried sum), with digit counts D on both sides of K and beyond 2K, on words from {0, 1, q-2, q-1, (q-1)/2,
 (q+1)/2} and on the worst case: a ciphertext whose every TrivGad digit is the constant -1 against hint slots that hold q-1, so that
@@ -33,7 +34,11 @@ pytestmark = pytest.mark.gpu
 
 U32 = (1 << 32) - 1
 CLASSES = list(range(3, 12))                                     # kmax; K = 0, 2, 3, 4, 5, 6, 7, 8, 8
-CLASS_K = {3: 0, 4: 2, 5: 3, 6: 4, 7: 5, 8: 6, 9: 7, 10: 8, 11: 8}
+CLASS_K = {2: 0, 3: 0, 4: 2, 5: 3, 6: 4, 7: 5, 8: 6, 9: 7, 10: 8, 11: 8}
+# kmax = 2 (K = 0): every prime from 1 431 655 766 up to 2^31, the reference's own moduli (1 543 651 201 ...) among them; 2q < 2^32 has
+# the least room at its top.  Run by the two tunnel engines and evalLin; the Tensor methods and the key switch run these primes as
+# LEVEL_RINGS["top_of_0"] below and in tests/test_gpu_word32_edges.py.
+TUNNEL_CLASSES = [2] + CLASSES
 
 
 def class_ring(m, kmax, L, end="top"):
@@ -54,7 +59,8 @@ TP_PAIRS = {1: (64, 128), 2: (128, 64), 8: (512, 64)}             # d_rel -> (r'
 # K = 8: a ring has at most 8 limbs and d_rel is 1, 2 or 8, so D = 9 and a non-multiple of 8 above 16 do not exist with TrivGad:
 # 10 and 16 stand in (16: a full group behind a carry), the BaseBGad 2 case below has D = 29 = 3 * 8 + 5, and the general-index
 # tunnels run D = 9 and 18.
-TP_TRIV = {3: [(1, 2), (2, 2)],
+TP_TRIV = {2: [(1, 2), (2, 2)],
+           3: [(1, 2), (2, 2)],
            4: [(1, 2), (1, 3), (1, 5)],
            5: [(1, 2), (1, 3), (2, 2), (1, 7)],
            6: [(1, 3), (2, 2), (1, 5), (2, 5)],
@@ -63,12 +69,12 @@ TP_TRIV = {3: [(1, 2), (2, 2)],
            9: [(2, 3), (1, 7), (8, 1), (8, 2)],
            10: [(1, 7), (8, 1), (2, 5), (8, 2)],
            11: [(1, 7), (8, 1), (2, 5), (8, 2)]}
-TP_CASES = [(kmax, d, L) for kmax in CLASSES for d, L in TP_TRIV[kmax]]
+TP_CASES = [(kmax, d, L) for kmax in TUNNEL_CLASSES for d, L in TP_TRIV[kmax]]
 TP_MODULI = (128, 512)                                           # max(r', s') of the pairs
 
 
 def test_the_two_power_digit_counts_cover_each_group_size():
-    for kmax in CLASSES:
+    for kmax in TUNNEL_CLASSES:
         K, Ds = CLASS_K[kmax], [d * L for d, L in TP_TRIV[kmax]]
         if K == 0:
             assert len(set(Ds)) == 2
@@ -130,7 +136,8 @@ def test_tunnel_twopower_group_size_is_per_limb(oracle_lib, rp, sp, gadget):
 # ---- general-index tunnels: k_tunnel_mac_e and the composed path -------------------------------------------------------------------
 GEN_PAIRS = {2: (40, 60), 3: (63, 105)}                           # d_rel -> (r', s'); moduli = 1 mod lcm = 120, 315
 # kmax -> (d_rel, L), D = d_rel L: the values next to K that 2 L and 3 L reach, and one >= 2K that is no multiple of K
-GEN_TRIV = {3: [(2, 1), (3, 1)],
+GEN_TRIV = {2: [(2, 1), (3, 1)],
+            3: [(2, 1), (3, 1)],
             4: [(2, 1), (3, 1), (3, 3)],
             5: [(2, 2), (2, 4)],
             6: [(2, 2), (3, 3)],
@@ -139,7 +146,7 @@ GEN_TRIV = {3: [(2, 1), (3, 1)],
             9: [(2, 4), (3, 5)],
             10: [(2, 4), (3, 3), (3, 6)],
             11: [(3, 3), (3, 6)]}
-GEN_CASES = [(kmax, d, L) for kmax in CLASSES for d, L in GEN_TRIV[kmax]]
+GEN_CASES = [(kmax, d, L) for kmax in TUNNEL_CLASSES for d, L in GEN_TRIV[kmax]]
 GEN_MODULI = (120, 315)
 # (tunnel_ep, tunnel_fused, tunnel_mac) of tests/test_gpu_tunnel.py::test_tunnel_hop_matches_the_oracle
 OPTION_SETS = ((1, 2, 1), (1, 4, 1), (1, 0, 1), (1, 0, 0), (0, 2, 1))
@@ -175,7 +182,7 @@ def _gen_tunnel_case(oracle_lib, rp, sp, qs, option_sets, minus_one, seed):
 
 
 def test_the_general_digit_counts_cover_each_group_size():
-    for kmax in CLASSES:
+    for kmax in TUNNEL_CLASSES:
         K, Ds = CLASS_K[kmax], [d * L for d, L in GEN_TRIV[kmax]]
         if K == 0:
             assert len(set(Ds)) == 2
@@ -212,7 +219,7 @@ PT_MODULI = (8, 12, 128)
 
 
 @pytest.mark.parametrize("r,s,p", PT_LIN_CASES)
-@pytest.mark.parametrize("kmax", CLASSES)
+@pytest.mark.parametrize("kmax", TUNNEL_CLASSES)
 def test_pt_eval_lin_at_the_top_of_each_class(r, s, p, kmax):
     """evalLin through a lifting ring on the two largest primes of the class: d_rel = 16 products per slot walk two or more groups
     at every K, d_rel = 6 sits at K - 1 .. K + 4."""
@@ -221,7 +228,8 @@ def test_pt_eval_lin_at_the_top_of_each_class(r, s, p, kmax):
     assert (r, s, p) in TP.LIN_CASES
     ys, xs, want = TP.lin_case(r, s, p)
     batch = len(xs)
-    lift, rr, rs = TP.lift_ring(s, f"class{kmax}"), TP.zp(r, p), TP.zp(s, p)
+    lift = TP.lift_ring(s, f"class{kmax}") if kmax >= 3 else A.Ring(s, class_ring(s, kmax, 2))      # lift_ring builds classes 3 .. 11
+    rr, rs = TP.zp(r, p), TP.zp(s, p)
     assert lift.word_bytes == 4 and all(lazy_group(q) == CLASS_K[kmax] for q in lift.qs)
     f = A.pt_linear(lift, TP.up(rs, ys), r)
     src, dst = TP.up(rr, xs), rs.alloc(batch)
