@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Randomised parity sweep on general cyclotomic indices: alch_ct_mul_relin (TrivGad), alch_ct_mul_full (TrivGad) and alch_ct_mod_switch
-on random indices m = 2^a 3^b 5^c 7^d 13^e with phi(m) <= 3000, random 1..5 moduli = 1 mod m (29..31 bits, or next to
+on random indices m = 2^a 3^b 5^c 7^d 11^e 13^f (a <= 5, b <= 5, c <= 3, d, e, f <= 2) with phi(m) <= 40960 -- the whole range
+alch_ring_create serves at 4-byte words; rings above 3000 coefficients are drawn with probability 0.15 and batch <= 2, the oracle's
+cost grows with them -- random 1..5 moduli = 1 mod m (29..31 bits, or next to
 the constants that choose dense_row's variant and the ends of the group-size classes: helpers.threshold_moduli), random batches and launch
 options (gen_fused, gen_nt, rs_lin), every result word compared with the general C restatement.  usage: tests/sweeps/fuzz_parity_gen.py [seconds] [seed]"""
 import os, random, sys, time
@@ -33,17 +35,19 @@ def main():
     t0, cases, tally = time.time(), 0, {}
     print(f"seed {seed}", flush=True)
     while time.time() - t0 < budget:
-        m = 2 ** rng.choice([0, 0, 1, 2, 3, 5]) * 3 ** rng.choice([0, 1, 2]) * 5 ** rng.choice([0, 1, 2]) * 7 ** rng.choice([0, 1]) * 13 ** rng.choice([0, 1])
+        big = rng.random() < 0.15                                   # a ring above 3000 coefficients
+        m = (2 ** rng.choice([0, 0, 1, 2, 3, 5]) * 3 ** rng.choice([0, 1, 2, 3, 4, 5] if big else [0, 1, 2]) * 5 ** rng.choice([0, 1, 2, 3] if big else [0, 1, 2])
+             * 7 ** rng.choice([0, 1, 2] if big else [0, 0, 1, 1, 2]) * 11 ** rng.choice([0, 0, 1, 1, 2]) * 13 ** rng.choice([0, 1, 2] if big else [0, 0, 1, 1, 2]))
         if m % 2 == 0 and m % 4 != 0: m *= 2                        # indices are not 2 mod 4
         n = phi(m)
-        if n < 4 or n > 3000 or m & (m - 1) == 0: continue           # two-power indices have their own sweep
+        if n < 4 or n > 40960 or (n > 3000) != big or m & (m - 1) == 0: continue   # two-power indices have their own sweep
         if n < 200 and rng.random() < 0.85: continue                 # mostly rings of a few hundred to 3000 coefficients
         L = rng.randint(1, 5)
         if rng.random() < 0.33: qs = threshold_moduli(rng, m, L)
         else: qs = primes_1_mod(m, L, lo=rng.choice([1 << 28, 1 << 29, (1 << 30) + (1 << 29), 715_000_000]))
         if max(qs) >= 1 << 31: continue
         rng.shuffle(qs)
-        batch = rng.randint(1, 9)
+        batch = rng.randint(1, 2) if big else rng.randint(1, 9)
         opts = {k: rng.choice(v) for k, v in OPTS.items() if rng.random() < 0.4}
         rnd = lambda c, q_: np.stack([np.stack([nprng.integers(0, q, size=n, dtype=np.int64) for q in q_], axis=1) for _ in range(c)])
         s_pre = None if rng.random() < 0.5 else [rng.randrange(1, q) for q in qs]
@@ -96,7 +100,7 @@ def main():
             if not (np.array_equal(got[2 * ct], want[ct][0]) and np.array_equal(got[2 * ct + 1], want[ct][1])):
                 print("MISMATCH", kind, dict(m=m, qs=qs, batch=batch, opts=opts, ct=ct, seed=seed)); return 1
         cases += 1
-        key = (kind, "phi < 200" if n < 200 else "phi < 1000" if n < 1000 else "phi <= 3000")
+        key = (kind, "phi < 200" if n < 200 else "phi < 1000" if n < 1000 else "phi <= 3000" if n <= 3000 else "phi <= 12288" if n <= 12288 else "phi <= 40960")
         tally[key] = tally.get(key, 0) + 1
         if cases % 25 == 0: print(f"{cases} cases, {time.time() - t0:.0f} s", flush=True)
     for k in sorted(tally): print(k, tally[k])

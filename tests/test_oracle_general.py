@@ -5,7 +5,8 @@ that could (SURVEY 8c -- parity unpinned):
      mulG == product with g, divG inverts it and fails exactly when it must, and a SymmSHE round trip DECRYPTS CORRECTLY
      through mulG / Dec-basis lifting / divG / twace (the only semantic check available, like Arithmetic.hs's PASS);
   2. oracle/lol_tensor_gen.c (sparse decompositions, as lol-cpp) == the model, on small indices and, by whole-index
-     direct evaluation, on the reference's real ciphertext indices H0' .. H5' (examples/Common.hs:49-54);
+     direct evaluation, on the reference's real ciphertext indices H0' .. H5' (examples/Common.hs:49-54) and on the large
+     indices of tests/test_gpu_general_structure.py (prime 11 up to 11^4, 3^10, the rings of exactly 160 KiB);
   3. the committed fixtures tests/golden/general_*.json (model-generated) == the C restatement.
 """
 import random
@@ -13,12 +14,17 @@ import random
 import numpy as np
 import pytest
 
-from helpers import load_golden, oracle_full_mul_general, primes_1_mod, to_aos
+from helpers import load_golden, oracle_full_mul_general, primes_1_mod, primes_below, to_aos
 from oracle import model_gen as G
 
 RLWR_QS = [1543651201, 689270401, 718099201, 720720001, 1556755201, 1567238401]
 H_PRIME = [11648, 29120, 43680, 54600, 27300, 20475]
-SMALL = [4, 16, 3, 9, 27, 12, 28, 45, 36, 91, 63, 225, 100, 455, 6, 125]
+SMALL = [4, 16, 3, 9, 27, 12, 28, 45, 36, 91, 63, 225, 100, 455, 6, 125,
+         # prime 11 alone, innermost, outermost, squared and cubed; 7^2, 7^3, 13^2 and 3^7 (tests/test_gpu_general_structure.py leans on these)
+         11, 33, 44, 77, 121, 143, 49, 343, 169, 1331, 2187]
+# the large indices of tests/test_gpu_general_structure.py: the fused / composed boundary, the LDS limit at either word size
+LARGE = [14641, 59049, 102400, 90112, 168960, 84480, 53760, 21609]
+LARGE_SAMPLED = [59049, 102400, 90112, 168960]      # phi = 39366, 40960, 40960, 40960: the whole direct evaluation takes 16 - 22 s each
 
 
 def lm(x):
@@ -135,6 +141,69 @@ def test_c_restatement_at_the_references_indices_by_direct_evaluation(oracle_lib
     assert np.array_equal(R.divg_pow(R.mulg_pow(x)), x) and np.array_equal(R.divg_dec(R.mulg_dec(x)), x)
     assert np.array_equal(R.l(R.linv(x)), x)
     assert R.mulg_crt(np.ones_like(x))[:, j].tolist() == G.g_crt(idx, RLWR_QS[j])
+
+
+def crt_def_at(a, idx, q, slots):
+    """G.crt_def restricted to the output slots given: slot s = sum_j a_j omega_m^(u(s) e(j)), evaluated directly (q < 2^31)."""
+    assert q < 1 << 31
+    n, m = idx.n, idx.m
+    w = G.omega_m(q, m)
+    powers = np.empty(m, dtype=np.uint64)
+    acc = 1
+    for t in range(m):
+        powers[t] = acc
+        acc = acc * w % q
+    ex = np.array([idx.pow_exponent(j) for j in range(n)], dtype=np.int64)
+    av = np.array([x % q for x in a], dtype=np.uint64)
+    return [int(((powers[(ex * idx.slot_unit(s)) % m] * av) % np.uint64(q)).sum(dtype=np.uint64) % np.uint64(q)) for s in slots]
+
+
+def sample_slots(idx, rng, per_axis=6):
+    """Output slots spread over every axis: the first and the last slot, and for every axis its first, its last and `per_axis` random
+    positions, each with the other axes at their first, at their last and at random positions; random slots on top up to 64."""
+    slots = {0, idx.n - 1}
+    for l, dim in enumerate(idx.dims):
+        for pos in [0, dim - 1] + [rng.randrange(dim) for _ in range(per_axis)]:
+            for others in ("first", "last", "random"):
+                at = [0 if others == "first" else d - 1 if others == "last" else rng.randrange(d) for d in idx.dims]
+                at[l] = pos
+                slots.add(idx.ravel(at))
+    while len(slots) < 64:
+        slots.add(rng.randrange(idx.n))
+    return sorted(slots)
+
+
+@pytest.mark.parametrize("m", LARGE)
+def test_c_restatement_at_the_large_structure_indices_by_direct_evaluation(oracle_lib, m):
+    """The indices tests/test_gpu_general_structure.py runs at the fused / composed boundary and at the LDS limit, on the two largest
+    primes = 1 (mod m) below 2^31: crt of one limb against the whole-index direct evaluation, and the homomorphism / mulG / divG / l
+    identities and the CRT image of g.  14641, 84480, 53760 and 21609 are evaluated whole (2 - 5 s); 59049, 102400, 90112 and 168960
+    (phi = 39366 .. 40960, 16 - 22 s whole) on a fixed, seeded sample of at least 64 output slots: the first and the last position and
+    random ones of every axis (sample_slots).  The sampled form is for phi > 12288 only."""
+    idx = G.Index(m)
+    qs = primes_below(m, 2, 1 << 31)
+    R = oracle_lib.GenRing(m, qs)
+    assert R.n == idx.n and R.has_crt
+    x = R.fill_uniform(m, 0)
+    cx = R.crt(x)
+    if m in LARGE_SAMPLED:
+        assert idx.n > 12288
+        slots = sample_slots(idx, random.Random(m))
+        assert len(slots) >= 64 and {0, idx.n - 1} <= set(slots)
+        assert [int(cx[s, 0]) for s in slots] == crt_def_at(x[:, 0].tolist(), idx, qs[0], slots)
+    else:
+        assert cx[:, 0].tolist() == G.crt_def(x[:, 0].tolist(), idx, qs[0])
+    rings = [(R, x, cx)]
+    if m == 84480:                                   # the GPU tests run this index on 8-byte words: the identities on the top of 2^62 too
+        R62 = oracle_lib.GenRing(m, primes_below(m, 2, 1 << 62))
+        x62 = R62.fill_uniform(m, 1)
+        rings.append((R62, x62, R62.crt(x62)))
+    for Rr, xr, cr in rings:
+        assert np.array_equal(Rr.crtinv(cr), xr)
+        assert np.array_equal(Rr.crt(Rr.mulg_pow(xr)), Rr.mulg_crt(cr))
+        assert np.array_equal(Rr.divg_pow(Rr.mulg_pow(xr)), xr) and np.array_equal(Rr.divg_dec(Rr.mulg_dec(xr)), xr)
+        assert np.array_equal(Rr.l(Rr.linv(xr)), xr)
+    assert R.mulg_crt(np.ones_like(x))[:, 0].tolist() == G.g_crt(idx, qs[0])
 
 
 def test_fixtures_tensor(oracle_lib):
