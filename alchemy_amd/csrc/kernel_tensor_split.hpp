@@ -5,9 +5,23 @@
 //
 // Gentleman-Sande order: the stages 14..1 of the n-point inverse act inside each half of the slots (sub-transform of
 // size n/2 with the big ring's twiddles, prefix = 2 + half, no n^-1); stage 0 pairs coefficient k of the two
-// halves.  Half 0's result waits in 32 registers per lane while half 1 is transformed; both are read from LDS in the
-// same lane-contiguous pattern, so stage 0, the n^-1 s scaling, the centred lift and the 16-byte digit stores are
-// lane-local.
+// halves.
+//
+// Three LDS trips per half for the 14 local stages (ALCH_TI_SPLIT_PASSES == 4, the product):
+//   on load   a lane holds the products of four ADJACENT slots (one 16-byte piece of a1 and b1).  Local stages 13 and
+//             12 pair slots at distance 1 and 2, inside the piece, so they run in registers before the piece is
+//             written to LDS; their three twiddles (a pair and a single word, lane-contiguous in the table) are
+//             fetched with the piece's operands.
+//   LB = 2    stages [8, 12): groups {64 h + lo + 4 k}, per-lane twiddles (four lanes share a group index)
+//   LB = 6    stages [4, 8):  wave-uniform twiddles
+//   LB = 10   stages [0, 4):  wave-uniform twiddles, KEEP: nothing is written back.  A lane owns the coefficients
+//             tid + 512 g + 1024 k of its half -- the same set for both halves -- so half 0's 32 values wait in
+//             registers while half 1 is transformed, and stage 0, the n^-1 s scaling, the centred lift and the digit
+//             stores are lane-local straight out of half 1's last pass.  For fixed (g, k) a wave stores 64
+//             consecutive coefficients (256 contiguous bytes) with dword buffer stores.
+// ALCH_TI_CLOSE_LDS = 1 writes the last pass back and reads both halves once more in the lane-contiguous layout for
+// 16-byte digit stores (four trips); ALCH_TI_SPLIT_PASSES == 5 is the earlier sequence (4 + 4 + 4 + 2 stages in LDS
+// and that closing trip: five), == 3 its radix-32 form.  DESIGN.md section 11 has the measurements.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ntt_engine.hpp"
@@ -15,6 +29,12 @@
 #ifndef ALCH_TI_SPLIT_PASSES
 #define ALCH_TI_SPLIT_PASSES 4
 #endif
+#ifndef ALCH_TI_CLOSE_LDS
+#define ALCH_TI_CLOSE_LDS 0
+#endif
+// stages 13 and 12 in registers on load; the closing epilogue straight out of the last pass
+#define ALCH_TI_ONLOAD (ALCH_TI_SPLIT_PASSES == 4)
+#define ALCH_TI_EPI_REGS (ALCH_TI_ONLOAD && !ALCH_TI_CLOSE_LDS)
 
 // experiment switch: cache policy of the operand loads (2 = non-temporal: read once by this kernel)
 #ifndef ALCH_TI_NT_IN
@@ -43,9 +63,11 @@ k_tensor_intt_split(DevRing<u32> R, const u32* __restrict__ a, const u32* __rest
     typedef u32 W;
     constexpr int LOGM = LOGN - 1, M = 1 << LOGM, LT = LOGN - 6, T = 1 << LT;
     typedef Geo<LOGM, LT> G;
-    static_assert(G::E == 32 && (LOGM - 2) % 4 == 0, "32 coefficients per lane, stages 4+4+4+2");
+    static_assert(G::E == 32 && (LOGM - 2) % 4 == 0, "32 coefficients per lane, stages 2 (on load) + 4 + 4 + 4");
     typedef u32 V __attribute__((ext_vector_type(4)));
+#if !ALCH_TI_EPI_REGS
     typedef int32_t SV __attribute__((ext_vector_type(4)));
+#endif
     constexpr int NV = G::E / 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     W* lds = reinterpret_cast<W*>(smem);
@@ -55,6 +77,9 @@ k_tensor_intt_split(DevRing<u32> R, const u32* __restrict__ a, const u32* __rest
     const auto rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<W*>(b), 0, (u32)((size_t)nct * 2 * L * (2 * M) * 4), 0x00020000);
     const auto rd = __builtin_amdgcn_make_buffer_rsrc(digits, 0, (u32)((size_t)nct * L * (2 * M) * 4), 0x00020000);
     const u32 lane16 = threadIdx.x * 16u;
+#if ALCH_TI_EPI_REGS
+    const u32 lane4 = threadIdx.x * 4u;
+#endif
     constexpr u32 ROW = (u32)(2 * M) * 4u, SLICE = (u32)T * 16u, HALF = (u32)M * 4u;
 #if ALCH_A_PARTIALS
     const auto rh = __builtin_amdgcn_make_buffer_rsrc(const_cast<W*>(hint), 0, (u32)((size_t)2 * L * L * (2 * M) * 4), 0x00020000);
@@ -70,15 +95,23 @@ k_tensor_intt_split(DevRing<u32> R, const u32* __restrict__ a, const u32* __rest
         const u32 drow = (ct * (u32)L + i) * ROW;
         const int rot = (int)((item ^ (item >> 3)) & (NV - 1));      // slice order rotated per item (HBM channels)
         const W* twi = R.twi[i];
-        V keep[NV];
+        W keep[G::E];
 #pragma unroll 1
         for (int half = 0; half < 2; ++half) {
             int tid = threadIdx.x;
             asm volatile("" : "+v"(tid));
+            const int prefix = 2 + half;
             // c2 = a1 b1 R^-1 (lazy) for this half of the slots -> LDS
 #pragma unroll
             for (int r = 0; r < NV; ++r) {
                 const u32 so = row + (u32)half * HALF + SLICE * (u32)((r + rot) & (NV - 1));
+#if ALCH_TI_ONLOAD
+                // the piece starts at slot b = 4 p: stage 13 groups b/2 and b/2 + 1, stage 12 group b/4
+                const int p = tid + T * ((r + rot) & (NV - 1));
+                typedef W W2 __attribute__((ext_vector_type(2)));
+                const W2 w13 = *reinterpret_cast<const W2*>(twi + (prefix << (LOGM - 1)) + 2 * p);
+                const W w12 = twi[(prefix << (LOGM - 2)) + p];
+#endif
                 const V va = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(ra, lane16, so, ALCH_TI_NT_IN));
                 const V vb = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rb, lane16, so, ALCH_TI_NT_IN));
 #if ALCH_A_PARTIALS
@@ -111,15 +144,56 @@ k_tensor_intt_split(DevRing<u32> R, const u32* __restrict__ a, const u32* __rest
                     ALCH_STORE_GUARD(o1v);
                 }
 #endif
-                V v;
+                W c[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = mont_mul_lazy(va[e], vb[e], q, qni);
+                for (int e = 0; e < 4; ++e) c[e] = mont_mul_lazy(va[e], vb[e], q, qni);
+#if ALCH_TI_ONLOAD
+                if constexpr (Q30) {
+                    bfly_inv4(c[0], c[1], w13[0], q, qni); bfly_inv4(c[2], c[3], w13[1], q, qni);
+                    bfly_inv4(c[0], c[2], w12, q, qni);    bfly_inv4(c[1], c[3], w12, q, qni);
+                } else {
+                    bfly_inv(c[0], c[1], (W)w13[0], q, qni);  bfly_inv(c[2], c[3], (W)w13[1], q, qni);
+                    bfly_inv(c[0], c[2], w12, q, qni);        bfly_inv(c[1], c[3], w12, q, qni);
+                }
+#endif
+                const V v = {c[0], c[1], c[2], c[3]};
                 *reinterpret_cast<V*>(&lds[swz<LOGM>((tid + T * ((r + rot) & (NV - 1))) * 4)]) = v;
             }
             lds_barrier();
             NoEpilogue none;
-            const int prefix = 2 + half;
-#if ALCH_TI_SPLIT_PASSES == 3
+            const W hq = (q - 1) >> 1;
+#if ALCH_TI_ONLOAD
+            ntt_pass<LOGM, LT, W, 8, 4, true, false, false, W, NoEpilogue&, false, Q30>(lds, twi, q, qni, (W)0, (W)0, tid, prefix, none);
+            lds_barrier();
+            ntt_pass<LOGM, LT, W, 4, 4, true, false, false, W, NoEpilogue&, false, Q30>(lds, twi, q, qni, (W)0, (W)0, tid, prefix, none);
+            lds_barrier();
+#if ALCH_TI_CLOSE_LDS
+            ntt_pass<LOGM, LT, W, 0, 4, true, false, false, W, NoEpilogue&, false, Q30>(lds, twi, q, qni, (W)0, (W)0, tid, prefix, none);
+            lds_barrier();
+#else
+            // x[k] = coefficient tid + T g + 1024 k of this half; half 0 waits in `keep`, half 1 closes: stage 0 with n^-1 s
+            // folded in, centred lift, digit stores (for fixed g, k a wave writes 256 contiguous bytes)
+            auto close = [&](int g, int, W* x) {
+                if (half == 0) {
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) keep[16 * g + k] = x[k];
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) {
+                        const W u = csub(keep[16 * g + k], q), y = csub(x[k], q);
+                        const W c0 = csub(mont_mul_lazy((W)(u + y), ninv_s, q, qni), q);
+                        const W c1 = csub(mont_mul_lazy((W)(u - y + q), w1ninv_s, q, qni), q);
+                        const int32_t z0 = c0 > hq ? (int32_t)c0 - (int32_t)q : (int32_t)c0;
+                        const int32_t z1 = c1 > hq ? (int32_t)c1 - (int32_t)q : (int32_t)c1;
+                        const u32 so = drow + 4u * (u32)(T * g + (k << (LOGM - 4)));
+                        __builtin_amdgcn_raw_buffer_store_b32(z0, rd, lane4, so, 0);
+                        __builtin_amdgcn_raw_buffer_store_b32(z1, rd, lane4, so + HALF, 0);
+                    }
+                }
+            };
+            ntt_pass<LOGM, LT, W, 0, 4, true, true, false, W, decltype(close)&, false, Q30>(lds, twi, q, qni, (W)0, (W)0, tid, prefix, close);
+#endif
+#elif ALCH_TI_SPLIT_PASSES == 3
             // 14 stages as 5 + 5 + 4: three LDS round trips per half instead of four (radix-32 groups: 32 coefficients and
             // up to 31 per-lane twiddles in registers -- affordable here, there are no accumulators to keep)
             ntt_pass<LOGM, LT, W, 9, 5, true, false, false, W, NoEpilogue&, false, Q30>(lds, twi, q, qni, (W)0, (W)0, tid, prefix, none);
@@ -138,19 +212,23 @@ k_tensor_intt_split(DevRing<u32> R, const u32* __restrict__ a, const u32* __rest
             ntt_pass<LOGM, LT, W, 0, 2, true, false, false, W, NoEpilogue&, false, Q30>(lds, twi, q, qni, (W)0, (W)0, tid, prefix, none);
             lds_barrier();
 #endif
+#if !ALCH_TI_EPI_REGS
             if (half == 0) {
 #pragma unroll
-                for (int r = 0; r < NV; ++r) keep[r] = *reinterpret_cast<const V*>(&lds[swz<LOGM>((tid + T * r) * 4)]);
+                for (int r = 0; r < NV; ++r) {
+                    const V lo = *reinterpret_cast<const V*>(&lds[swz<LOGM>((tid + T * r) * 4)]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) keep[4 * r + e] = lo[e];
+                }
             } else {
                 // stage 0 with n^-1 s folded in, centred lift, digit stores (lane-contiguous, 16 bytes per lane)
-                const W hq = (q - 1) >> 1;
 #pragma unroll
                 for (int r = 0; r < NV; ++r) {
                     const V hi = *reinterpret_cast<const V*>(&lds[swz<LOGM>((tid + T * r) * 4)]);
                     SV z0, z1;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const W x = csub(keep[r][e], q), y = csub(hi[e], q);
+                        const W x = csub(keep[4 * r + e], q), y = csub(hi[e], q);
                         const W c0 = csub(mont_mul_lazy((W)(x + y), ninv_s, q, qni), q);
                         const W c1 = csub(mont_mul_lazy((W)(x - y + q), w1ninv_s, q, qni), q);
                         z0[e] = c0 > hq ? (int32_t)c0 - (int32_t)q : (int32_t)c0;
@@ -163,6 +241,7 @@ k_tensor_intt_split(DevRing<u32> R, const u32* __restrict__ a, const u32* __rest
                     ALCH_STORE_GUARD(z1);
                 }
             }
+#endif
             lds_barrier();                      // LDS is refilled next
         }
     }

@@ -40,9 +40,12 @@ struct Geo {
 // ALCH_LDS_PAD = 1: four padding words after every 64 (LDS grows by 1/16).  Additive over operands with
 //   disjoint bits (pad(a | b) = pad(a) + pad(b)), so element k is the group base plus a compile-time constant,
 //   which the LDS instructions take as an immediate offset: no address arithmetic per access.
-// Both are bank-conflict free for the four access shapes the passes use (LB = 0: 16 contiguous words per lane,
+// Both are bank-conflict free for the five access shapes the passes use (LB = 0: 16 contiguous words per lane,
 // 128-bit accesses; LB = 4: runs of 16 lanes 256 words apart; LB >= 6: 64 consecutive words; lane-contiguous
-// 16-byte pieces): see DESIGN.md.
+// 16-byte pieces; LB = 2, k_tensor_intt_split's first LDS pass: runs of 4 lanes 64 words apart): see DESIGN.md.
+// LB = 2, element k of lane t is coefficient 64 (t >> 2) + 4 k + (t & 3).  Padded: word 68 (t >> 2) + 4 k + (t & 3),
+// bank (4 (t >> 2) + 4 k + (t & 3)) mod 64, distinct over the 64 lanes of a wave.  XOR: bank 4 (k ^ (t >> 2)) + (t & 3),
+// distinct as well.
 #ifndef ALCH_LDS_PAD
 #define ALCH_LDS_PAD 1
 #endif
@@ -102,11 +105,26 @@ __device__ __forceinline__ void lds_barrier() {
 // Local stage r of a pass needs the CNT = 2^r consecutive table words tw[first .. first+CNT), first a
 // multiple of CNT: one vector load per four words instead of one dword load per butterfly.  When every
 // lane of the wave wants the same words (UNIFORM), the index is made wave-uniform so the loads become
-// scalar (s_load) and the twiddles live in SGPRs.
+// scalar (s_load) and the twiddles live in SGPRs.  The compiler selects a scalar load only where it can prove that
+// no store of the kernel reaches the table; a kernel that stores to global memory inside its item loop
+// (k_tensor_intt_split, k_crt_half) got vector loads of sixty-four equal words instead, in order behind its own stores
+// on vmcnt.  The tables are written at ring creation only and never while a kernel that reads them runs, so one-word
+// tables are read through the constant address space (ALCH_TW_CONSTANT_AS = 0: the plain pointer, for A/B builds).
+#ifndef ALCH_TW_CONSTANT_AS
+#define ALCH_TW_CONSTANT_AS 1
+#endif
 template <typename W, int CNT, bool UNIFORM>
 __device__ __forceinline__ void load_tw(const W* __restrict__ tw, int first, W (&w)[CNT]) {   // W: table word
     if constexpr (UNIFORM) {
         const int f = __builtin_amdgcn_readfirstlane(first);
+#if defined(__HIP_DEVICE_COMPILE__) && ALCH_TW_CONSTANT_AS
+        if constexpr (sizeof(W) <= 8) {
+            const __attribute__((address_space(4))) W* ct = (const __attribute__((address_space(4))) W*)(tw + f);
+#pragma unroll
+            for (int c = 0; c < CNT; ++c) w[c] = ct[c];
+            return;
+        }
+#endif
 #pragma unroll
         for (int c = 0; c < CNT; ++c) w[c] = tw[f + c];
     } else if constexpr (sizeof(W) == 16) {               // two-word Shoup twiddles: one 16-byte load each
