@@ -178,6 +178,10 @@ static bool bytes_overlap(const void* a, size_t na, const void* b, size_t nb) {
     const char *x = reinterpret_cast<const char*>(a), *y = reinterpret_cast<const char*>(b);
     return x < y + nb && y < x + na;
 }
+// The overlap rule of the element-wise entry points (include/alchemy_hip.h, "Overlapping ranges"): a written range may START where an
+// operand's range starts -- every lane reads the words it writes before it writes them, in the vector and in the one-word forms -- and
+// any other common byte is a race between lanes: refused.
+static bool shifted_overlap(const void* w, size_t nw, const void* r, size_t nr) { return w != r && bytes_overlap(w, nw, r, nr); }
 static int fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
@@ -2047,6 +2051,10 @@ static int buf_pointwise(alch_buf* dst, const alch_buf* a, const alch_buf* b, si
     if (a->ring != dst->ring || b->ring != dst->ring) return fail(ALCH_E_INVALID, "buffers belong to different rings");
     if (count > dst->n_elems || count > a->n_elems || count > b->n_elems) return fail(ALCH_E_INVALID, "count out of bounds");
     alch_ring* r = dst->ring;
+    const size_t bytes = count * elem_bytes(r);
+    if (count && (shifted_overlap(dst->dptr, bytes, a->dptr, bytes) || shifted_overlap(dst->dptr, bytes, b->dptr, bytes)))
+        return fail(ALCH_E_INVALID, std::string(op == PW_MUL ? "alch_buf_mul" : op == PW_ADD ? "alch_buf_add" : "alch_buf_sub") +
+                                        ": dst overlaps an operand without starting where it starts");
     BIND(r);
     if (!r->has_crt && op == PW_MUL) return fail(ALCH_E_NO_CRT, "pointwise products need the CRT basis; this ring has none");
     if (r->word == 4) {
@@ -2278,6 +2286,8 @@ extern "C" int alch_buf_scale(alch_buf* dst, const alch_buf* src, size_t count, 
     if (dst->ring != src->ring) return fail(ALCH_E_INVALID, "buffers belong to different rings");
     if (count > dst->n_elems || count > src->n_elems) return fail(ALCH_E_INVALID, "count out of bounds");
     alch_ring* r = dst->ring;
+    if (count && shifted_overlap(dst->dptr, count * elem_bytes(r), src->dptr, count * elem_bytes(r)))
+        return fail(ALCH_E_INVALID, "alch_buf_scale: dst overlaps src without starting where it starts");
     BIND(r);
     return ALCH_BY_WORD(r, do_scale, r, dst->dptr, src->dptr, count, s);
 } catch (...) { return abi_catch(); }
@@ -2290,6 +2300,9 @@ extern "C" int alch_buf_decompose_triv(const alch_buf* src, size_t src_index, al
     if (src_index >= src->n_elems || !range_ok(dst_first, (size_t)r->L, dst->n_elems)) return fail(ALCH_E_INVALID, "element range out of bounds");
     const char* c = reinterpret_cast<const char*>(src->dptr) + src_index * elem_bytes(r);
     char* dig = reinterpret_cast<char*>(dst->dptr) + dst_first * elem_bytes(r);
+    // every word of the source element is read by L lanes, one per digit: it must lie outside all L digits
+    if (bytes_overlap(dig, (size_t)r->L * elem_bytes(r), c, elem_bytes(r)))
+        return fail(ALCH_E_INVALID, "alch_buf_decompose_triv: the source element lies inside the L digits that are written");
     const size_t total = (size_t)r->L * elem_words(r);
     if (r->word == 4) hipLaunchKernelGGL((k_decompose_triv<u32>), dim3(ew_grid(total)), dim3(256), 0, r->stream, r->d32, (const u32*)c, (u32*)dig, r->balanced ? 1 : 0);
     else hipLaunchKernelGGL((k_decompose_triv<u64>), dim3(ew_grid(total)), dim3(256), 0, r->stream, r->d64, (const u64*)c, (u64*)dig, r->balanced ? 1 : 0);
@@ -2334,9 +2347,13 @@ extern "C" int alch_ct_add_public(alch_buf* dst, const alch_buf* src, size_t bat
     if (!r->has_crt) return fail(ALCH_E_UNSUPPORTED, "scalar products are implemented for rings with Montgomery constants (prime moduli) only");
     if (!pairs_ok(batch, dst->n_elems) || !pairs_ok(batch, src->n_elems) || pub_index >= pub->n_elems) return fail(ALCH_E_INVALID, "count out of bounds");
     if (batch == 0) return ALCH_OK;
+    const char* pp = reinterpret_cast<const char*>(pub->dptr) + pub_index * elem_bytes(r);
+    if (shifted_overlap(dst->dptr, 2 * batch * elem_bytes(r), src->dptr, 2 * batch * elem_bytes(r)))
+        return fail(ALCH_E_INVALID, "alch_ct_add_public: dst overlaps src without starting where it starts");
+    if (bytes_overlap(dst->dptr, 2 * batch * elem_bytes(r), pp, elem_bytes(r)))       // read by the lanes of every ciphertext
+        return fail(ALCH_E_INVALID, "alch_ct_add_public: the public element lies inside the 2*batch elements of dst that are written");
     BIND(r);
     const size_t words = 2 * batch * elem_words(r);
-    const char* pp = reinterpret_cast<const char*>(pub->dptr) + pub_index * elem_bytes(r);
     if (r->word == 4) {
         typedef u32 W;
         Scal<W> sm; scal_to_mont<W>(r, s, 1, sm);
@@ -2526,9 +2543,13 @@ extern "C" int alch_buf_mul_public(alch_buf* dst, const alch_buf* src, const alc
     if (src->ring != r || pub->ring != r) return fail(ALCH_E_INVALID, "buffers belong to different rings");
     if (!r->has_crt) return fail(ALCH_E_NO_CRT, "this ring has no CRT basis");
     if (count > dst->n_elems || count > src->n_elems || pub_index >= pub->n_elems) return fail(ALCH_E_INVALID, "count out of bounds");
+    const char* pp = reinterpret_cast<const char*>(pub->dptr) + pub_index * elem_bytes(r);
+    if (count && shifted_overlap(dst->dptr, count * elem_bytes(r), src->dptr, count * elem_bytes(r)))
+        return fail(ALCH_E_INVALID, "alch_buf_mul_public: dst overlaps src without starting where it starts");
+    if (count && bytes_overlap(dst->dptr, count * elem_bytes(r), pp, elem_bytes(r)))  // read by the lanes of every element
+        return fail(ALCH_E_INVALID, "alch_buf_mul_public: the public element lies inside the count elements of dst that are written");
     BIND(r);
     const size_t words = count * elem_words(r);
-    const char* pp = reinterpret_cast<const char*>(pub->dptr) + pub_index * elem_bytes(r);
     if (r->word == 4) hipLaunchKernelGGL((k_mul_bcast<u32>), dim3(ew_grid(words)), dim3(256), 0, r->stream, r->d32, (u32*)dst->dptr, (const u32*)src->dptr, (const u32*)pp, words);
     else hipLaunchKernelGGL((k_mul_bcast<u64>), dim3(ew_grid(words)), dim3(256), 0, r->stream, r->d64, (u64*)dst->dptr, (const u64*)src->dptr, (const u64*)pp, words);
     HIP_TRY(hipGetLastError());
@@ -2540,9 +2561,13 @@ extern "C" int alch_buf_add_public(alch_buf* cts, const alch_buf* pub, size_t pu
     alch_ring* r = cts->ring;
     if (pub->ring != r) return fail(ALCH_E_INVALID, "buffers belong to different rings");
     if (!pairs_ok(batch, cts->n_elems) || pub_index >= pub->n_elems) return fail(ALCH_E_INVALID, "count out of bounds");
+    const char* pp = reinterpret_cast<const char*>(pub->dptr) + pub_index * elem_bytes(r);
+    // only the c0 components (even elements) are written, but the ciphertext range is refused as a whole, c1 components included: one
+    // rule for the three public-element entry points and for alch_buf_add_bcast
+    if (batch && bytes_overlap(cts->dptr, 2 * batch * elem_bytes(r), pp, elem_bytes(r)))
+        return fail(ALCH_E_INVALID, "alch_buf_add_public: the public element lies inside the 2*batch elements of cts");
     BIND(r);
     const size_t words = batch * elem_words(r);
-    const char* pp = reinterpret_cast<const char*>(pub->dptr) + pub_index * elem_bytes(r);
     if (r->word == 4) hipLaunchKernelGGL((k_add_bcast<u32>), dim3(ew_grid(words)), dim3(256), 0, r->stream, r->d32, (u32*)cts->dptr, (const u32*)pp, batch);
     else hipLaunchKernelGGL((k_add_bcast<u64>), dim3(ew_grid(words)), dim3(256), 0, r->stream, r->d64, (u64*)cts->dptr, (const u64*)pp, batch);
     HIP_TRY(hipGetLastError());
@@ -2891,7 +2916,11 @@ extern "C" int alch_ct_mul_relin(alch_ring* r, const alch_hint* hint, const alch
     BIND(r);
     if (!pairs_ok(batch, a->n_elems) || !pairs_ok(batch, b->n_elems) || !pairs_ok(batch, out->n_elems))
         return fail(ALCH_E_INVALID, "buffers must hold 2*batch ring elements");
-    if (out == a || out == b) return fail(ALCH_E_INVALID, "out must not alias an input");
+    // by bytes, not by handle: a view of an operand is another handle over the same words, and the fused kernels read the operands
+    // chunk by chunk while earlier chunks write out
+    if (bytes_overlap(out->dptr, 2 * batch * elem_bytes(r), a->dptr, 2 * batch * elem_bytes(r)) ||
+        bytes_overlap(out->dptr, 2 * batch * elem_bytes(r), b->dptr, 2 * batch * elem_bytes(r)))
+        return fail(ALCH_E_INVALID, "alch_ct_mul_relin: out must not alias an input");
     const void* pa = a->dptr;
     const void* pb = b->dptr;
     int rc;
@@ -3371,6 +3400,9 @@ static int mul_full_base2(const alch_hint* hint, const alch_buf* a, const alch_b
     if (!rh->has_crt) return fail(ALCH_E_NO_CRT, "the hint's ring has no CRT basis");
     if (batch == 0) return ALCH_OK;
     if (!pairs_ok(batch, a->n_elems) || !pairs_ok(batch, b->n_elems) || !pairs_ok(batch, out->n_elems)) return fail(ALCH_E_INVALID, "buffers must hold 2*batch ring elements");
+    if (bytes_overlap(out->dptr, 2 * batch * elem_bytes(rout), a->dptr, 2 * batch * elem_bytes(rin)) ||      // one ring may serve both sides
+        bytes_overlap(out->dptr, 2 * batch * elem_bytes(rout), b->dptr, 2 * batch * elem_bytes(rin)))
+        return fail(ALCH_E_INVALID, "alch_ct_mul_full: out must not alias an input");
     BIND(rh);
     const int dup = in_down ? 0 : rh->L - rin->L;
     alch_buf *ua = nullptr, *ub = nullptr, *ks = nullptr, *c2h = nullptr;
@@ -3432,6 +3464,11 @@ extern "C" int alch_ct_mul_full(const alch_hint* hint, const alch_buf* a, const 
     BIND(rh);
     if (!pairs_ok(batch, a->n_elems) || !pairs_ok(batch, b->n_elems) || !pairs_ok(batch, out->n_elems))
         return fail(ALCH_E_INVALID, "buffers must hold 2*batch ring elements");
+    // operands and output may live on ONE suffix ring of the hint's (mul_ at q: up to q', key switch, down to q), so out can be a
+    // view into an operand: refused by bytes, as in alch_ct_mul_relin
+    if (bytes_overlap(out->dptr, 2 * batch * elem_bytes(rout), a->dptr, 2 * batch * elem_bytes(rin)) ||
+        bytes_overlap(out->dptr, 2 * batch * elem_bytes(rout), b->dptr, 2 * batch * elem_bytes(rin)))
+        return fail(ALCH_E_INVALID, "alch_ct_mul_full: out must not alias an input");
     // everything runs on the hint ring's stream, behind the work of the other two rings (one wait serves both where they share a stream)
     const bool two_others = rout->stream != rin->stream;
     int rc;
@@ -3813,6 +3850,9 @@ extern "C" int alch_ct_tunnel(const alch_tunnel* t, const alch_buf* in, alch_buf
     if (flags & ~(unsigned)(ALCH_POW_IN | ALCH_POW_OUT)) return fail(ALCH_E_INVALID, "unknown flag");
     if (batch == 0) return ALCH_OK;
     if (!pairs_ok(batch, in->n_elems) || !pairs_ok(batch, out->n_elems)) return fail(ALCH_E_INVALID, "buffers must hold 2*batch ring elements");
+    // a tunnel from a ring to itself (R' = S', the key switch alone) has input and output on one ring: out may be a view into in
+    if (bytes_overlap(out->dptr, 2 * batch * elem_bytes(out->ring), in->dptr, 2 * batch * elem_bytes(in->ring)))
+        return fail(ALCH_E_INVALID, "alch_ct_tunnel: out must not alias the input");
     alch_ring* rs = t->rs;
     alch_ring* rr = t->rr;
     BIND(rs);
@@ -3900,6 +3940,7 @@ extern "C" int alch_ct_mod_switch(const alch_buf* in, alch_buf* out, size_t batc
     const bool up = rout->L > rin->L;
     if (rin->L == rout->L || !(up ? is_suffix_ring(rin, rout) : is_suffix_ring(rout, rin)))
         return fail(ALCH_E_INVALID, "the smaller ring's moduli must be the last limbs of the bigger ring's (same index and word size)");
+    // no overlap check: rin->L != rout->L, so in and out belong to two rings, a view keeps its parent's ring and two allocations share no byte
     if (batch == 0) return ALCH_OK;
     if (!pairs_ok(batch, in->n_elems) || !pairs_ok(batch, out->n_elems)) return fail(ALCH_E_INVALID, "buffers must hold 2*batch ring elements");
     alch_ring* rw = up ? rout : rin;                          // the ring whose stream carries the work
@@ -3926,6 +3967,7 @@ extern "C" int alch_ct_mod_switch_deg(const alch_buf* in, alch_buf* out, size_t 
     if (batch > in->n_elems / per || batch > out->n_elems / per)
         return fail(ALCH_E_INVALID, "alch_ct_mod_switch_deg: buffers must hold (degree + 1) * batch ring elements");
     if (!rin->has_crt || !rout->has_crt) return fail(ALCH_E_NO_CRT, "alch_ct_mod_switch_deg: modSwitch runs on rings with a CRT basis");
+    // no overlap check: the limb counts differ, so in and out belong to two rings and to two allocations (see alch_ct_mod_switch)
     if (batch == 0) return ALCH_OK;
     alch_ring* rw = up ? rout : rin;                          // the ring whose stream carries the work
     alch_ring* ro = up ? rin : rout;
@@ -3949,6 +3991,7 @@ extern "C" int alch_buf_rescale_drop0(const alch_buf* src, alch_buf* dst, size_t
     for (int j = 1; j < rs->L; ++j)
         if (rs->q[j] != rd->q[j - 1]) return fail(ALCH_E_INVALID, "destination limbs must equal source limbs 1..L-1");
     if (count > src->n_elems || count > dst->n_elems) return fail(ALCH_E_INVALID, "count out of bounds");
+    // no overlap check: rd has one limb fewer than rs, so src and dst belong to two rings and to two allocations
     const size_t total = count * (size_t)rd->L * rd->n;
     HIP_TRY(hipStreamSynchronize(rd->stream));
     if (rs->word == 4)
@@ -3970,6 +4013,7 @@ extern "C" int alch_buf_rescale_add0(const alch_buf* src, alch_buf* dst, size_t 
     for (int j = 0; j < rs->L; ++j)
         if (rs->q[j] != rd->q[j + 1]) return fail(ALCH_E_INVALID, "destination limbs 1..L must equal the source limbs");
     if (count > src->n_elems || count > dst->n_elems) return fail(ALCH_E_INVALID, "count out of bounds");
+    // no overlap check: rd has one limb more than rs, so src and dst belong to two rings and to two allocations
     uint64_t qa[MAXL] = {0};
     for (int j = 1; j < rd->L; ++j) qa[j] = rd->q[0] % rd->q[j];
     const size_t total = count * (size_t)rd->L * rd->n;

@@ -136,6 +136,9 @@ extern "C" int alch_buf_embed(alch_buf* dst, const alch_buf* src, size_t count, 
     const ExtTab* t = nullptr;
     int rc = ext_tables(small, big, &t);
     if (rc != ALCH_OK || count == 0) return rc;
+    // equal indices make one ring serve as both (embed = the identity gather): dst can then be a view into src
+    if (bytes_overlap(dst->dptr, count * elem_bytes(big), src->dptr, count * elem_bytes(small)))
+        return fail(ALCH_E_INVALID, "alch_buf_embed: dst must not overlap src");
     BIND(big);
     if ((rc = ext_order(big, small, true)) != ALCH_OK) return rc;
     const alch_buf* from = src;
@@ -164,6 +167,8 @@ extern "C" int alch_buf_twace(alch_buf* dst, const alch_buf* src, size_t count, 
     const ExtTab* t = nullptr;
     int rc = ext_tables(small, big, &t);
     if (rc != ALCH_OK || count == 0) return rc;
+    if (bytes_overlap(dst->dptr, count * elem_bytes(small), src->dptr, count * elem_bytes(big)))         // equal indices: one ring on both sides
+        return fail(ALCH_E_INVALID, "alch_buf_twace: dst must not overlap src");
     BIND(small);
     if ((rc = ext_order(small, big, true)) != ALCH_OK) return rc;
     if (basis != ALCH_BASIS_CRT) {                                             // twacePowDec: the same positions on either basis
@@ -201,6 +206,8 @@ extern "C" int alch_buf_coeffs(alch_buf* dst, const alch_buf* src, size_t count)
     if (rc != ALCH_OK) return rc;
     if (count > src->n_elems || count > dst->n_elems / (size_t)t->d_rel) return fail(ALCH_E_INVALID, "dst must hold d_rel * count elements");
     if (count == 0) return ALCH_OK;
+    if (bytes_overlap(dst->dptr, (size_t)t->d_rel * count * elem_bytes(small), src->dptr, count * elem_bytes(big)))   // equal indices: d_rel = 1
+        return fail(ALCH_E_INVALID, "alch_buf_coeffs: dst must not overlap src");
     BIND(small);
     if ((rc = ext_order(small, big, true)) != ALCH_OK) return rc;
     rc = ALCH_BY_WORD(small, ext_gather, small, src->dptr, dst->dptr, t->coeffs, big->n, small->n, t->d_rel, count);

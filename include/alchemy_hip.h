@@ -214,6 +214,25 @@ int alch_buf_free(alch_buf *buf);
  * of `decompose` be handed on as single-element Tensor values without copies.  alch_buf_free of a view releases only the handle;
  * the parent must outlive its views (the Haskell side keeps the parent's ForeignPtr alive from the view's finalizer). */
 int alch_buf_view(const alch_buf *parent, size_t first, size_t count, alch_buf **out);
+/* Overlapping ranges.  Views make two handles cover the same bytes, so every entry point that takes several ranges of one ring
+ * compares BYTE ranges, not handles.  The rule: the range a call writes must share no byte with a range it reads -- touching
+ * ranges (adjacent views of one parent) are fine -- and a violation is ALCH_E_INVALID with the function's name in
+ * alch_last_error() and nothing launched.  Ranges that are only read may overlap freely (a == b is legal everywhere).  Where
+ * an entry point differs:
+ *   alch_buf_mul / _add / _sub / _scale   dst may START where a, b or src starts (any subset of them): in place
+ *   alch_buf_mul_public, alch_ct_add_public   the same for dst / src; pub[pub_index] must lie outside the count (2 * batch)
+ *                                         elements of dst, and may lie inside src
+ *   alch_buf_add_public                   in place by definition; pub[pub_index] must lie outside all 2 * batch elements of cts,
+ *                                         the c1 components (odd elements) included although only c0 is written
+ *   alch_buf_decompose_triv               element src_index must lie outside dst[dst_first, dst_first + L)
+ *   alch_buf_add_bcast, alch_pt_mul, alch_pt_rescale, alch_buf_lift, alch_buf_tensor_op, alch_buf_copy
+ *                                         dst may start where its source starts (alch_buf_copy: a no-op); one[index] as pub above
+ *   alch_ct_add                           out may start where an operand of the result's degree starts
+ *   alch_hint_from_buf, alch_tunnel_create, alch_pt_linear_create   copy their sources: the sources may be overwritten afterwards
+ * Entry points between two rings whose limb counts differ (alch_ct_mod_switch(_deg), alch_buf_rescale_drop0 / _add0) cannot be
+ * given overlapping ranges: a view keeps its parent's ring.  Those that accept one ring on both sides (alch_buf_embed / _twace /
+ * _coeffs with equal indices, alch_ct_tunnel from a ring to itself, alch_ct_mul_full with operands and result on one ring)
+ * follow the rule without exception. */
 int alch_buf_elems(const alch_buf *buf, size_t *n_elems);
 /* Device address and size of the buffer (limb-major words, see above) for zero-copy hand-off to other device
  * code on the same GPU -- RCCL collectives that gather result batches, a caller's own kernels.
@@ -234,7 +253,8 @@ int alch_buf_crtinv(alch_buf *buf, size_t first, size_t count);
 int alch_buf_mul(alch_buf *dst, const alch_buf *a, const alch_buf *b, size_t count);
 int alch_buf_add(alch_buf *dst, const alch_buf *a, const alch_buf *b, size_t count);
 int alch_buf_sub(alch_buf *dst, const alch_buf *a, const alch_buf *b, size_t count);
-/* dst = src * s_j per limb (toLSD / toMSD scalars of SymmSHE, any basis); dst may equal src. */
+/* dst = src * s_j per limb (toLSD / toMSD scalars of SymmSHE, any basis); dst may equal src; a shifted overlap is refused
+ * ("Overlapping ranges" above, as for the three calls before this one). */
 int alch_buf_scale(alch_buf *dst, const alch_buf *src, size_t count, const uint64_t *s);
 /* Batched l / lInv / mulG / divG on elements [first, first+count); basis = ALCH_BASIS_*.  alch_buf_divg returns
  * ALCH_NOT_DIVISIBLE when any element of the range is not divisible (the range is then unspecified). */

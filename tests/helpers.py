@@ -179,6 +179,24 @@ def centred_extreme_words(rng, count, n, qs):
     return extreme_words(rng, count, n, qs, extremes=centred_extremes)
 
 
+def carve(ring, host, *spans):
+    """(parent, [views]): one device buffer holding `host` ((count, n, L) int64) and one alch_buf_view of it per span (first, count)
+    -- the operands of one overlap case (tests/test_gpu_overlap_contract.py): adjacent, coinciding or shifted ranges of one parent."""
+    parent = ring.upload(host)
+    return parent, [parent.view(first, count) for first, count in spans]
+
+
+def assert_parent_unchanged(parent, host, written=()):
+    """Every element of `parent` outside the `written` spans (first, count) still holds the uploaded words; returns the download."""
+    got = parent.download()
+    keep = np.ones(len(host), dtype=bool)
+    for first, count in written:
+        keep[first:first + count] = False
+    assert got.shape == np.asarray(host).shape
+    assert np.array_equal(got[keep], np.asarray(host)[keep]), "words outside the written range changed"
+    return got
+
+
 def assert_reduced(got, qs):
     """Every stored word of a (..., L) result lies in [0, q_j)."""
     got = np.asarray(got)
