@@ -214,7 +214,10 @@ int alch_buf_free(alch_buf *buf);
  * of `decompose` be handed on as single-element Tensor values without copies.  alch_buf_free of a view releases only the handle;
  * the parent must outlive its views (the Haskell side keeps the parent's ForeignPtr alive from the view's finalizer). */
 int alch_buf_view(const alch_buf *parent, size_t first, size_t count, alch_buf **out);
-/* Overlapping ranges.  Views make two handles cover the same bytes, so every entry point that takes several ranges of one ring
+/* Footprint.  A call stores nothing outside the ranges it is documented to write -- the words next to a view belong to the caller --
+ * and leaves its inputs as they were; a count or an offset that leads past the end of a handle is ALCH_E_INVALID even where the
+ * handle's parent has the room (DESIGN section 19 lists the span every entry point writes).
+ * Overlapping ranges.  Views make two handles cover the same bytes, so every entry point that takes several ranges of one ring
  * compares BYTE ranges, not handles.  The rule: the range a call writes must share no byte with a range it reads -- touching
  * ranges (adjacent views of one parent) are fine -- and a violation is ALCH_E_INVALID with the function's name in
  * alch_last_error() and nothing launched.  Ranges that are only read may overlap freely (a == b is legal everywhere).  Where

@@ -197,6 +197,36 @@ def assert_parent_unchanged(parent, host, written=()):
     return got
 
 
+class Gapped:
+    """Operand and result placement of one sweep case (tests/sweeps/fuzz_parity.py, fuzz_parity_gen.py): with `on`, every operand and
+    the result are views in the interior of parents of their own, `margin` uniform elements before and `margin` + `tail` behind
+    (tail: what a kernel's rounded-up last tile could reach), and check() asserts every word outside the result range as uploaded
+    (tests/test_gpu_footprint.py's rule); without, plain buffers, as the sweeps always had."""
+
+    def __init__(self, on, nprng, margin=3, tail=16):
+        self.on, self.nprng, self.margin, self.tail, self.parents = on, nprng, margin, tail, []
+
+    def _fill(self, ring, count):
+        return np.ascontiguousarray(np.stack([self.nprng.integers(0, q, size=(count, ring.n), dtype=np.int64) for q in ring.qs], axis=2))
+
+    def _place(self, ring, host, count, written):
+        before, behind = self._fill(ring, self.margin), self._fill(ring, self.margin + self.tail)
+        whole = np.concatenate([before, host if host is not None else self._fill(ring, count), behind])
+        parent = ring.upload(whole)
+        self.parents.append((parent, whole, [(self.margin, count)] if written else []))
+        return parent.view(self.margin, count)
+
+    def operand(self, ring, host):
+        return self._place(ring, np.asarray(host), len(host), False) if self.on else ring.upload(host)
+
+    def result(self, ring, count):
+        return self._place(ring, None, count, True) if self.on else ring.alloc(count)
+
+    def check(self):
+        for parent, whole, written in self.parents:
+            assert_parent_unchanged(parent, whole, written)
+
+
 def assert_reduced(got, qs):
     """Every stored word of a (..., L) result lies in [0, q_j)."""
     got = np.asarray(got)

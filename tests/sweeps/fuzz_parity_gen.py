@@ -4,7 +4,9 @@ on random indices m = 2^a 3^b 5^c 7^d 11^e 13^f (a <= 5, b <= 5, c <= 3, d, e, f
 alch_ring_create serves at 4-byte words; rings above 3000 coefficients are drawn with probability 0.15 and batch <= 2, the oracle's
 cost grows with them -- random 1..5 moduli = 1 mod m (29..31 bits, or next to
 the constants that choose dense_row's variant and the ends of the group-size classes: helpers.threshold_moduli), random batches and launch
-options (gen_fused, gen_nt, rs_lin), every result word compared with the general C restatement.  usage: tests/sweeps/fuzz_parity_gen.py [seconds] [seed]"""
+options (gen_fused, gen_nt, rs_lin), every result word compared with the general C restatement.  With probability 1/2 the operands and
+the result of a case are views in the interior of gapped parents (helpers.Gapped) and every word outside the result range is asserted as
+uploaded.  usage: tests/sweeps/fuzz_parity_gen.py [seconds] [seed]"""
 import os, random, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -12,7 +14,7 @@ import numpy as np
 import alchemy_amd as A
 from alchemy_amd import capi
 from oracle import cref
-from helpers import oracle_full_mul_general, primes_1_mod, threshold_moduli
+from helpers import Gapped, oracle_full_mul_general, primes_1_mod, threshold_moduli
 
 OPTS = {"gen_fused": [0, 1], "gen_nt": [0, 128, 256, 512], "rs_lin": [0, 1], "scratch_mib": [1, 64]}
 
@@ -32,7 +34,7 @@ def main():
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else int(time.time())
     rng, nprng = random.Random(seed), np.random.default_rng(seed)
     cref.build()
-    t0, cases, tally = time.time(), 0, {}
+    t0, cases, views, tally = time.time(), 0, 0, {}
     print(f"seed {seed}", flush=True)
     while time.time() - t0 < budget:
         big = rng.random() < 0.15                                   # a ring above 3000 coefficients
@@ -52,13 +54,14 @@ def main():
         rnd = lambda c, q_: np.stack([np.stack([nprng.integers(0, q, size=n, dtype=np.int64) for q in q_], axis=1) for _ in range(c)])
         s_pre = None if rng.random() < 0.5 else [rng.randrange(1, q) for q in qs]
         kind = rng.choice(["relin", "full", "modswitch"]) if L >= 2 else "relin"
+        gp = Gapped(rng.random() < 0.5, nprng)                      # half the cases: operands and result as interior views of gapped parents
         try:
             if kind == "relin":
                 g, o = A.Ring(m, qs), cref.GenRing(m, qs)
                 for k, v in opts.items(): g.set_option(k, v)
                 hint, a, b = rnd(2 * L, qs), rnd(2 * batch, qs), rnd(2 * batch, qs)
-                out = g.alloc(2 * batch)
-                g.ct_mul_relin(g.hint_load(hint), g.upload(a), g.upload(b), out, batch, s_pre=s_pre)
+                out = gp.result(g, 2 * batch)
+                g.ct_mul_relin(g.hint_load(hint), gp.operand(g, a), gp.operand(g, b), out, batch, s_pre=s_pre)
                 got = out.download()
                 want = [o.ct_mul_relin(list(hint), a[2 * ct], a[2 * ct + 1], b[2 * ct], b[2 * ct + 1], s_pre=s_pre) for ct in range(batch)]
             elif kind == "full":
@@ -69,8 +72,8 @@ def main():
                 pow_out = rng.random() < 0.3
                 hint, a, b = rnd(2 * L, qs), rnd(2 * batch, qs[L - l_in:]), rnd(2 * batch, qs[L - l_in:])
                 sp = None if s_pre is None else s_pre[L - l_in:]
-                out = rout.alloc(2 * batch)
-                capi.ct_mul_full(rh.hint_load(hint), rin.upload(a), rin.upload(b), out, batch, s_pre=sp, flags=capi.ALCH_POW_OUT if pow_out else 0)
+                out = gp.result(rout, 2 * batch)
+                capi.ct_mul_full(rh.hint_load(hint), gp.operand(rin, a), gp.operand(rin, b), out, batch, s_pre=sp, flags=capi.ALCH_POW_OUT if pow_out else 0)
                 got = out.download()
                 want = [oracle_full_mul_general(cref, m, qs, l_in, l_out, list(hint), a[2 * ct], a[2 * ct + 1], b[2 * ct], b[2 * ct + 1], sp,
                                                 pow_out=pow_out) for ct in range(batch)]
@@ -79,8 +82,8 @@ def main():
                 rin, rout = A.Ring(m, qs), A.Ring(m, qs[ddn:])
                 for k, v in opts.items(): rin.set_option(k, v); rout.set_option(k, v)
                 x = rnd(2 * batch, qs)
-                out = rout.alloc(2 * batch)
-                capi.ct_mod_switch(rin.upload(x), out, batch)
+                out = gp.result(rout, 2 * batch)
+                capi.ct_mod_switch(gp.operand(rin, x), out, batch)
                 got = out.download()
                 want = []
                 for ct in range(batch):
@@ -99,12 +102,16 @@ def main():
         for ct in range(batch):
             if not (np.array_equal(got[2 * ct], want[ct][0]) and np.array_equal(got[2 * ct + 1], want[ct][1])):
                 print("MISMATCH", kind, dict(m=m, qs=qs, batch=batch, opts=opts, ct=ct, seed=seed)); return 1
-        cases += 1
+        try:
+            gp.check()                                              # every word outside the result range is as uploaded
+        except AssertionError as e:
+            print("FOOTPRINT", kind, e, dict(m=m, qs=qs, batch=batch, opts=opts, seed=seed)); return 1
+        cases += 1; views += gp.on
         key = (kind, "phi < 200" if n < 200 else "phi < 1000" if n < 1000 else "phi <= 3000" if n <= 3000 else "phi <= 12288" if n <= 12288 else "phi <= 40960")
         tally[key] = tally.get(key, 0) + 1
         if cases % 25 == 0: print(f"{cases} cases, {time.time() - t0:.0f} s", flush=True)
     for k in sorted(tally): print(k, tally[k])
-    print(f"OK: {cases} random general-index cases bit-exact against the oracle (seed {seed})")
+    print(f"OK: {cases} random general-index cases bit-exact against the oracle, {views} of them on interior views of gapped parents with every margin and operand as uploaded (seed {seed})")
     return 0
 
 
