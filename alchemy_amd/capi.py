@@ -14,6 +14,13 @@ ALCH_E_INVALID, ALCH_E_NOT_PRIME, ALCH_E_NO_CRT, ALCH_E_UNSUPPORTED = -1, -2, -3
 ALCH_E_NO_DEVICE, ALCH_E_HIP, ALCH_E_NOMEM, ALCH_E_INTERNAL = -5, -6, -7, -8
 ALCH_POW_IN, ALCH_POW_OUT = 1, 2
 ALCH_GAD_TRIV, ALCH_GAD_BASE2 = 0, 1
+
+
+def ALCH_GAD_BASEPOW2(w: int) -> int:
+    """BaseBGad 2^w, 1 <= w <= 16 (the header's macro); w = 1 means exactly ALCH_GAD_BASE2."""
+    return 0x100 | int(w)
+
+
 ALCH_NOT_DIVISIBLE = 1
 ALCH_BASIS_POW, ALCH_BASIS_DEC, ALCH_BASIS_CRT = 0, 1, 2
 # ops of alch_buf_tensor_op (the unary Tensor methods on device-resident elements)
@@ -43,6 +50,7 @@ SYMBOLS = [
     "alch_ct_add",
     "alch_gauss_table", "alch_gauss_plan", "alch_buf_gauss_dec", "alch_ct_encrypt",
     "alch_ct_ks_hint", "alch_ct_ks_hint_part",
+    "alch_gadget_digits", "alch_decompose_baseb",
 ]
 
 
@@ -133,6 +141,8 @@ def load_library():
         "alch_divg_pow": [VP, P64], "alch_divg_dec": [VP, P64], "alch_divg_crt": [VP, P64],
         "alch_decompose_triv": [VP, P64, P64],
         "alch_decompose_base2": [VP, P64, P64, C.POINTER(C.c_int)],
+        "alch_decompose_baseb": [VP, C.c_int, P64, P64, C.POINTER(C.c_int)],
+        "alch_gadget_digits": [VP, C.c_int, C.POINTER(C.c_int)],
         "alch_buf_alloc": [VP, C.c_size_t, C.POINTER(VP)],
         "alch_buf_free": [VP],
         "alch_buf_elems": [VP, C.POINTER(C.c_size_t)],
@@ -358,6 +368,15 @@ class Ring:
         _check(self._l.alch_decompose_base2(self._h, _p64(c), _p64(out), C.byref(nd)))
         return [out[i] for i in range(nd.value)]
 
+    def decompose_baseb(self, c_pow, gadget: int = ALCH_GAD_BASE2):
+        """The digits of one Pow-basis element under any BaseBGad code (ALCH_GAD_BASE2, ALCH_GAD_BASEPOW2(w))."""
+        c = np.ascontiguousarray(c_pow, dtype=np.int64)
+        nd = C.c_int()
+        _check(self._l.alch_decompose_baseb(self._h, gadget, None, None, C.byref(nd)))
+        out = np.zeros((nd.value, self.n, self.L), dtype=np.int64)
+        _check(self._l.alch_decompose_baseb(self._h, gadget, _p64(c), _p64(out), C.byref(nd)))
+        return [out[i] for i in range(nd.value)]
+
     # --- Tensor methods towards a ring of a multiple index (self = the small ring), host buffers
     def _ext(self, fn, big: "Ring", a, out_shape):
         a = np.ascontiguousarray(a, dtype=np.int64)
@@ -391,11 +410,9 @@ class Ring:
         return Hint(self, h)
 
     def gadget_digits(self, gadget: int = ALCH_GAD_TRIV) -> int:
-        """Digits (= hint rows) of a gadget on this ring: L for TrivGad, sum_i ceil(log2 q_i) for BaseBGad 2."""
-        if gadget == ALCH_GAD_TRIV:
-            return self.L
+        """Digits (= hint rows) of a gadget on this ring: L for TrivGad, sum_i ceil(ceil(log2 q_i) / w) for BaseBGad 2^w."""
         nd = C.c_int()
-        _check(self._l.alch_decompose_base2(self._h, None, None, C.byref(nd)))
+        _check(self._l.alch_gadget_digits(self._h, gadget, C.byref(nd)))
         return nd.value
 
     def hint_from_buf(self, buf: "Buf", gadget: int = ALCH_GAD_TRIV) -> "Hint":

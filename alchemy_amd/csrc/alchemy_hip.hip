@@ -399,8 +399,9 @@ __global__ void k_decompose_triv(DevRing<W> R, const W* c, W* digits, int balanc
 // BaseBGad 2 decompose + reduce of one Pow-basis element.  One thread per (source limb i, coefficient k) walks
 // the ceil(log2 q_i) digits (balanced remainder in {0,-1}, top digit absorbs the rest) and writes each one
 // reduced into every limb.  first_digit[i] = index of limb i's first digit, kd[i] = its digit count.
-template <typename W>
-__global__ void k_decompose_base2(DevRing<W> R, const W* c, W* digits, Scal<u32> first_digit, Scal<u32> kd, u32 D) {
+// P2: BaseBGad 2^gw, gw >= 2 -- kd[i] = ceil(ceil(log2 q_i) / gw) digits by the closed form of hint_gadget.hpp (pow2_digit).
+template <typename W, bool P2 = false>
+__global__ void k_decompose_base2(DevRing<W> R, const W* c, W* digits, Scal<u32> first_digit, Scal<u32> kd, u32 D, u32 gw) {
     typedef typename Signed<W>::type SW;
     const size_t n = (size_t)R.n;
     const size_t L = (size_t)R.L;
@@ -412,9 +413,13 @@ __global__ void k_decompose_base2(DevRing<W> R, const W* c, W* digits, Scal<u32>
         const W qi = R.mod[i].q;
         const W x = c[i * n + k];
         SW v = x > ((qi - 1) >> 1) ? (SW)x - (SW)qi : (SW)x;
+        SW ct = 0;                                       // P2: c_t of the closed form, c_(t+1) = c_t 2^gw + 2^(gw-1)
         for (u32 t = 0; t < kd.v[i]; ++t) {
             SW d;
-            if (t + 1 < kd.v[i]) {
+            if constexpr (P2) {
+                d = hintgad::pow2_digit<SW>(v, gw, t, t + 1 == kd.v[i], ct);
+                if (t + 1 < kd.v[i]) ct = (SW)(ct << gw) | (SW)((SW)1 << (gw - 1));   // c_k itself may not fit the word
+            } else if (t + 1 < kd.v[i]) {
                 d = v & 1 ? (SW)-1 : (SW)0;          // v mod 2 in {0,1}; remainder 1 is taken as -1 (2r >= b)
                 v = (v - d) / 2;
             } else {
@@ -1513,7 +1518,8 @@ extern "C" int alch_select_limbs(const uint64_t* moduli, int n_moduli, int op, i
                                  int* L_hint, int* L_out, int* p_noise_in) try {
     if (!moduli || n_moduli < 1 || p_noise_out < 0) return fail(ALCH_E_INVALID, "alch_select_limbs: bad argument");
     if (op != ALCH_OP_MUL && op != ALCH_OP_TUNNEL) return fail(ALCH_E_INVALID, "alch_select_limbs: unknown op");
-    if (gadget != ALCH_GAD_TRIV && gadget != ALCH_GAD_BASE2) return fail(ALCH_E_INVALID, "unknown gadget");
+    const int gw = hintgad::gadget_width(gadget);
+    if (gw < 0) return fail(ALCH_E_INVALID, "alch_select_limbs: unknown gadget");
     const int MinUnits = (int)std::ceil(12 / 6.1), MulPNoise = (int)std::ceil(18 / 6.1), KSAccumPNoise = (int)std::ceil(12 / 6.1),
               Max32BitUnits = (int)std::ceil(30.5 / 6.1), TunnelPNoise = (int)std::ceil(6 / 6.1);
     // prefixLen: length of the shortest nonempty prefix whose units sum to >= h; total = that prefix's units
@@ -1530,7 +1536,10 @@ extern "C" int alch_select_limbs(const uint64_t* moduli, int n_moduli, int op, i
     int tot_in = 0;
     const int lin = op == ALCH_OP_MUL ? prefix(p + MulPNoise + MinUnits, &tot_in)   // PreMul_: Units2CTPNoise (TotalUnits zqs (CTPNoise2Units (p :+ MulPNoise)))
                                       : prefix(p + TunnelPNoise + MinUnits, &tot_in);
-    const int ks_units = p + KSAccumPNoise + (gadget == ALCH_GAD_TRIV ? Max32BitUnits : 0);   // KSPNoise, KSPNoise2Units
+    // KSPNoise, KSPNoise2Units: the reference defines it for TrivGad (+ Max32BitUnits) and BaseBGad 2 (+ 0) only.  BaseBGad 2^w is this
+    // library's own rule, w - 1 more bits of digit in units of 6.1: + ceil((w - 1) / 6.1), which gives + 0 at w = 1 and reproduces
+    // Max32BitUnits for a 30.5-bit digit.
+    const int ks_units = p + KSAccumPNoise + (gw == 0 ? Max32BitUnits : (int)std::ceil((gw - 1) / 6.1));
     const int lh = prefix(ks_units, nullptr);
     if (lout < 0 || lin < 0 || lh < 0)
         return fail(ALCH_E_INVALID, "alch_select_limbs: the moduli do not hold enough noise units (PT2CT: \"You need more/bigger moduli!\")");
@@ -2214,13 +2223,15 @@ extern "C" int alch_decompose_triv(alch_ring* r, const int64_t* c_pow, int64_t* 
     return alch_buf_download(s.b, 1, (size_t)r->L, digits);
 } catch (...) { return abi_catch(); }
 
-// BaseBGad 2 layout: limb i owns ceil(log2 q_i) digits starting at first[i]; returns their total.
-static int base2_layout(const alch_ring* r, Scal<u32>& first, Scal<u32>& kd) {
+// The one predicate on gadget codes (hint_gadget.hpp): 0 TrivGad, w >= 1 BaseBGad 2^w, -1 unknown.
+using hintgad::gadget_width;
+
+// BaseBGad 2^w layout: limb i owns ceil(ceil(log2 q_i) / w) digits starting at first[i]; returns their total.
+static int base2_layout(const alch_ring* r, Scal<u32>& first, Scal<u32>& kd, u32 w) {
     int D = 0;
     for (int j = 0; j < MAXL; ++j) { first.v[j] = 0; kd.v[j] = 0; }
     for (int i = 0; i < r->L; ++i) {
-        int k = 0;
-        for (u64 v = 1; v < r->q[i]; v <<= 1) ++k;
+        const int k = (int)hintgad::digits_pow2(r->q[i], w);
         first.v[i] = (u32)D;
         kd.v[i] = (u32)k;
         D += k;
@@ -2228,16 +2239,26 @@ static int base2_layout(const alch_ring* r, Scal<u32>& first, Scal<u32>& kd) {
     return D;
 }
 
+// gadget: a code gadget_width accepts.
 static int gadget_digits(const alch_ring* r, int gadget) {
-    if (gadget == ALCH_GAD_TRIV) return r->L;
+    const int w = gadget_width(gadget);
+    if (w == 0) return r->L;
     Scal<u32> f, k;
-    return base2_layout(r, f, k);
+    return base2_layout(r, f, k, (u32)w);
 }
 
-extern "C" int alch_decompose_base2(alch_ring* r, const int64_t* c_pow, int64_t* digits, int* n_digits) try {
-    if (!r) return fail(ALCH_E_INVALID, "null ring");
+// k_decompose_base2 for `ny` elements on the ring's stream: the base-2 instantiation for w = 1, the closed form above it.
+template <typename W>
+static void launch_decompose_baseb(alch_ring* r, hipStream_t stream, const DevRing<W>& R, unsigned ny, const W* src, W* dst,
+                                   const Scal<u32>& first, const Scal<u32>& kd, u32 D, u32 w) {
+    const dim3 grid(ew_grid(elem_words(r)), ny);
+    if (w > 1) hipLaunchKernelGGL((k_decompose_base2<W, true>), grid, dim3(256), 0, stream, R, src, dst, first, kd, D, w);
+    else hipLaunchKernelGGL((k_decompose_base2<W, false>), grid, dim3(256), 0, stream, R, src, dst, first, kd, D, w);
+}
+
+static int decompose_baseb(alch_ring* r, u32 w, const int64_t* c_pow, int64_t* digits, int* n_digits) {
     Scal<u32> first, kd;
-    const int D = base2_layout(r, first, kd);
+    const int D = base2_layout(r, first, kd, w);
     if (n_digits) *n_digits = D;
     if (!digits) return ALCH_OK;
     if (!c_pow) return fail(ALCH_E_INVALID, "null argument");
@@ -2246,11 +2267,29 @@ extern "C" int alch_decompose_base2(alch_ring* r, const int64_t* c_pow, int64_t*
     if (rc != ALCH_OK) return rc;
     if ((rc = alch_buf_upload(s.b, 0, 1, c_pow)) != ALCH_OK) return rc;
     char* dig = reinterpret_cast<char*>(s.b->dptr) + elem_bytes(r);
-    const size_t total = elem_words(r);
-    if (r->word == 4) hipLaunchKernelGGL((k_decompose_base2<u32>), dim3(ew_grid(total)), dim3(256), 0, r->stream, r->d32, (const u32*)s.b->dptr, (u32*)dig, first, kd, (u32)D);
-    else hipLaunchKernelGGL((k_decompose_base2<u64>), dim3(ew_grid(total)), dim3(256), 0, r->stream, r->d64, (const u64*)s.b->dptr, (u64*)dig, first, kd, (u32)D);
+    if (r->word == 4) launch_decompose_baseb<u32>(r, r->stream, r->d32, 1, (const u32*)s.b->dptr, (u32*)dig, first, kd, (u32)D, w);
+    else launch_decompose_baseb<u64>(r, r->stream, r->d64, 1, (const u64*)s.b->dptr, (u64*)dig, first, kd, (u32)D, w);
     HIP_TRY(hipGetLastError());
     return alch_buf_download(s.b, 1, (size_t)D, digits);
+}
+
+extern "C" int alch_decompose_base2(alch_ring* r, const int64_t* c_pow, int64_t* digits, int* n_digits) try {
+    if (!r) return fail(ALCH_E_INVALID, "null ring");
+    return decompose_baseb(r, 1, c_pow, digits, n_digits);
+} catch (...) { return abi_catch(); }
+
+extern "C" int alch_decompose_baseb(alch_ring* r, int gadget, const int64_t* c_pow, int64_t* digits, int* n_digits) try {
+    if (!r) return fail(ALCH_E_INVALID, "alch_decompose_baseb: null ring");
+    const int w = gadget_width(gadget);
+    if (w < 1) return fail(ALCH_E_INVALID, "alch_decompose_baseb: unknown gadget (a BaseBGad code: ALCH_GAD_BASE2 or ALCH_GAD_BASEPOW2(1 .. 16))");
+    return decompose_baseb(r, (u32)w, c_pow, digits, n_digits);
+} catch (...) { return abi_catch(); }
+
+extern "C" int alch_gadget_digits(const alch_ring* r, int gadget, int* D) try {
+    if (!r || !D) return fail(ALCH_E_INVALID, "alch_gadget_digits: null argument");
+    if (gadget_width(gadget) < 0) return fail(ALCH_E_INVALID, "alch_gadget_digits: unknown gadget");
+    *D = gadget_digits(r, gadget);
+    return ALCH_OK;
 } catch (...) { return abi_catch(); }
 
 // ------------------------------------------------------------------------------------------------------
@@ -2258,7 +2297,7 @@ extern "C" int alch_decompose_base2(alch_ring* r, const int64_t* c_pow, int64_t*
 // ------------------------------------------------------------------------------------------------------
 static int hint_from_device(alch_ring* r, int gadget, const void* src_crt, alch_hint** out) {
     BIND(r);
-    if (gadget != ALCH_GAD_TRIV && gadget != ALCH_GAD_BASE2) return fail(ALCH_E_INVALID, "unknown gadget");
+    if (gadget_width(gadget) < 0) return fail(ALCH_E_INVALID, "alch_hint_load / alch_hint_from_buf: unknown gadget");
     const int digits = gadget_digits(r, gadget);
     const size_t elems = 2 * (size_t)digits;
     void* p = nullptr;
@@ -2312,7 +2351,7 @@ extern "C" int alch_buf_decompose_triv(const alch_buf* src, size_t src_index, al
 
 extern "C" int alch_hint_load(alch_ring* r, int gadget, const int64_t* host_crt, alch_hint** out) try {
     if (!r || !host_crt || !out) return fail(ALCH_E_INVALID, "null argument");
-    if (gadget != ALCH_GAD_TRIV && gadget != ALCH_GAD_BASE2) return fail(ALCH_E_INVALID, "unknown gadget");
+    if (gadget_width(gadget) < 0) return fail(ALCH_E_INVALID, "alch_hint_load: unknown gadget");
     const size_t elems = 2 * (size_t)gadget_digits(r, gadget);
     ScratchBuf s;
     int rc = scratch_get(r, elems, &s.b);
@@ -2325,7 +2364,7 @@ extern "C" int alch_hint_load(alch_ring* r, int gadget, const int64_t* host_crt,
 
 extern "C" int alch_hint_from_buf(alch_ring* r, int gadget, const alch_buf* src, alch_hint** out) try {
     if (!r || !src || !out) return fail(ALCH_E_INVALID, "null argument");
-    if (gadget != ALCH_GAD_TRIV && gadget != ALCH_GAD_BASE2) return fail(ALCH_E_INVALID, "unknown gadget");
+    if (gadget_width(gadget) < 0) return fail(ALCH_E_INVALID, "alch_hint_from_buf: unknown gadget");
     if (src->ring != r || src->n_elems < 2 * (size_t)gadget_digits(r, gadget))
         return fail(ALCH_E_INVALID, "hint source needs 2 ring elements per gadget digit");
     return hint_from_device(r, gadget, src->dptr, out);
@@ -2642,7 +2681,7 @@ static void gen_suffix_view(alch_ring* r, int u, DevRing<W>& d, GenDev<W>& g) {
 
 // The fused general-index key switch (k_gen_tensor_inv + k_gen_ks, kernel_gen.hpp): TrivGad, 32-bit words, n <= 12288.
 static bool gen_ks_fused(const alch_ring* r, const alch_hint* hint) {
-    return r->gen && r->word == 4 && hint->gadget == ALCH_GAD_TRIV && r->n <= (u32)(GEN_KS_T * GEN_KS_NPT) && r->opts.gen_fused;
+    return r->gen && r->word == 4 && gadget_width(hint->gadget) == 0 && r->n <= (u32)(GEN_KS_T * GEN_KS_NPT) && r->opts.gen_fused;
 }
 
 template <typename W>
@@ -2677,7 +2716,8 @@ struct KsStage {
     bool have_c2;               // c2 arrives on the powerful basis of r: no tensor product, no c2 scratch
     bool c2_both;               // with have_c2: the caller filled the stage's own layout -- c2 (Pow) at scratch, its CRT copy behind it, digits after
                                 // both (alch_ct_key_switch_quad: the TrivGad forms below read the diagonal digits from the CRT copy)
-    bool base2;
+    bool base2;                 // BaseBGad 2^gw
+    u32 gw;                     // log2 of its base
     bool fused_digits;          // TrivGad: decompose + reduce in the digit transforms' loader; the diagonal digits are c2's CRT copy
     bool gen_fused;             // k_gen_tensor_inv + k_gen_ks
     bool no_digits;             // the one-kernel forms (k_ks_accum_split, k_gen_ks) keep no digits in HBM: only c2 in both bases
@@ -2696,8 +2736,9 @@ template <typename W>
 static KsStage<W> ks_stage_plan(alch_ring* r, const alch_hint* hint, int dup, bool have_c2) {
     KsStage<W> s{};
     s.hint = hint; s.dup = dup; s.have_c2 = have_c2;
-    s.base2 = hint->gadget == ALCH_GAD_BASE2;
-    s.D = s.base2 ? (u32)base2_layout(r, s.first, s.kd) : (u32)r->L;
+    s.gw = (u32)gadget_width(hint->gadget);
+    s.base2 = s.gw > 0;
+    s.D = s.base2 ? (u32)base2_layout(r, s.first, s.kd, s.gw) : (u32)r->L;
     s.fused_digits = !s.base2 && (split_ring(r) || r->gen);
     s.gen_fused = !have_c2 && gen_ks_fused(r, hint);
     s.no_digits = s.fused_digits && ((!r->gen && r->opts.split_fused) || s.gen_fused);
@@ -2767,7 +2808,7 @@ static int ks_stage(alch_ring* r, const KsStage<W>& s, const W* a, const W* b, c
         nc.op = OP_CRT_BASE2;
         nc.data = dig;
         nc.npoly = now * (size_t)s.D * (size_t)L;
-        nc.b2_first = s.first; nc.b2_kd = s.kd; nc.b2_D = s.D;
+        nc.b2_first = s.first; nc.b2_kd = s.kd; nc.b2_D = s.D; nc.b2_w = s.gw;
         if ((rc = launch(r, nc, "crt_base2")) != ALCH_OK) return rc;
     } else {
         for (size_t y0 = 0; y0 < now; y0 += 32768) {             // grid.y is 16-bit
@@ -2775,8 +2816,7 @@ static int ks_stage(alch_ring* r, const KsStage<W>& s, const W* a, const W* b, c
             const W* src = c2pow + y0 * elem_words(r);
             W* dst = dig + y0 * s.D * elem_words(r);
             if (s.base2)
-                hipLaunchKernelGGL((k_decompose_base2<W>), dim3(ew_grid(elem_words(r)), ny), dim3(256), 0, r->stream,
-                                   dev_ring<W>(r), src, dst, s.first, s.kd, s.D);
+                launch_decompose_baseb<W>(r, r->stream, dev_ring<W>(r), ny, src, dst, s.first, s.kd, s.D, s.gw);
             else
                 hipLaunchKernelGGL((k_decompose_triv<W>), dim3(ew_grid((size_t)L * elem_words(r)), ny), dim3(256), 0,
                                    r->stream, dev_ring<W>(r), src, dst, r->balanced ? 1 : 0);
@@ -2944,8 +2984,8 @@ extern "C" int alch_ct_mul_relin(alch_ring* r, const alch_hint* hint, const alch
     }
     // split rings (a limb-polynomial is twice an LDS-resident transform), TrivGad: the same two-launch structure as the LDS-resident sizes
     // since round 3 (k_tensor_crtinv_split + k_ks_accum_split<FROM_OPS>); option split_fused < 2 keeps the composed forms
-    const bool split_two = split_ring(r) && !r->gen && hint->gadget == ALCH_GAD_TRIV && r->opts.split_fused >= 2;
-    if (!split_two && (hint->gadget == ALCH_GAD_BASE2 || split_ring(r) || r->gen))
+    const bool split_two = split_ring(r) && !r->gen && gadget_width(hint->gadget) == 0 && r->opts.split_fused >= 2;
+    if (!split_two && (gadget_width(hint->gadget) > 0 || split_ring(r) || r->gen))
         rc = ALCH_BY_WORD(r, do_mul_relin_unfused, r, hint, pa, pb, out->dptr, batch, s_pre);
     else
         rc = ALCH_BY_WORD(r, do_mul_relin, r, hint, pa, pb, out->dptr, batch, s_pre);
@@ -3455,7 +3495,7 @@ extern "C" int alch_ct_mul_full(const alch_hint* hint, const alch_buf* a, const 
     alch_ring* rin = a->ring;
     alch_ring* rout = out->ring;
     if (b->ring != rin) return fail(ALCH_E_INVALID, "operands belong to different rings");
-    if (hint->gadget != ALCH_GAD_TRIV) return mul_full_base2(hint, a, b, out, batch, s_pre, flags);
+    if (gadget_width(hint->gadget) > 0) return mul_full_base2(hint, a, b, out, batch, s_pre, flags);
     if (!is_suffix_ring(rin, rh)) return fail(ALCH_E_INVALID, "operand moduli must be the last limbs of the hint's ring (same word size)");
     if (!is_suffix_ring(rout, rh)) return fail(ALCH_E_INVALID, "output moduli must be the last limbs of the hint's ring (same word size)");
     if (rh->L - rout->L > MAXDROP) return fail(ALCH_E_UNSUPPORTED, "at most 3 limbs dropped per call");
@@ -3520,7 +3560,7 @@ static int tunnel_to_mont(alch_ring* rs, void* dst, const void* src, size_t elem
 extern "C" int alch_tunnel_create(alch_ring* rr, alch_ring* rs, int gadget, const alch_buf* lin_crt, const alch_buf* ks_crt, alch_tunnel** out) try {
     if (!rr || !rs || !lin_crt || !ks_crt || !out) return fail(ALCH_E_INVALID, "null argument");
     *out = nullptr;
-    if (gadget != ALCH_GAD_TRIV && gadget != ALCH_GAD_BASE2) return fail(ALCH_E_INVALID, "unknown gadget");
+    if (gadget_width(gadget) < 0) return fail(ALCH_E_INVALID, "alch_tunnel_create: unknown gadget");
     if (!rr->has_crt || !rs->has_crt) return fail(ALCH_E_UNSUPPORTED, "tunnelling runs on rings with a CRT basis");
     if (rr->gen != rs->gen)
         return fail(ALCH_E_UNSUPPORTED, "tunnelling between a two-power ring with m >= 32 and a general-index ring (composite m, or two-power m < 32) is not served");
@@ -3620,14 +3660,15 @@ static int do_tunnel(const alch_tunnel* t, alch_ring* rin, const void* in, void*
     alch_ring* rs = t->rs;
     const int L = rs->L, dup = rr->L - rin->L;
     const u32 D = t->d_rel;
-    const bool base2 = t->gadget == ALCH_GAD_BASE2;
+    const u32 bw = (u32)gadget_width(t->gadget);     // BaseBGad 2^bw; 0: TrivGad
+    const bool base2 = bw > 0;
     // compact: embedded coefficients and digits hold the L - dup non-zero limbs only (TrivGad; BaseBGad 2 keeps the
     // full layout with explicit zero limbs)
     const bool compact = dup > 0 && !base2;
     const u32 Lx = compact ? (u32)(L - dup) : (u32)L, xoff = compact ? (u32)dup : 0u;
     const u32 GD = base2 ? (u32)t->digits : Lx;     // gadget digits per embedded coefficient
     Scal<u32> b2first, b2kd;
-    if (base2) base2_layout(rs, b2first, b2kd);
+    if (base2) base2_layout(rs, b2first, b2kd, bw);
     // rx: the ring the E'-coefficients are transformed in -- E' itself when the tunnel has its ring (the CRT over S' of an embedded
     // element is its CRT over E' replicated: k_tunnel_lin / k_hint_mac read it through slot_e), else S' with the coefficients embedded
     alch_ring* rx = t->re ? t->re : rs;
@@ -3707,7 +3748,7 @@ static int do_tunnel(const alch_tunnel* t, alch_ring* rin, const void* in, void*
         if (base2) {                                 // BaseBGad 2 (examples/Tunnel.hs:24): decompose + reduce in the transforms' loader
             GenCall<W> g = gx;
             g.op = GEN_CRT_BASE2; g.src = reinterpret_cast<const W*>(x1); g.data = reinterpret_cast<W*>(dig);
-            g.npoly = now * (size_t)D * (size_t)GD * (size_t)L; g.b2_first = b2first; g.b2_kd = b2kd; g.b2_D = GD;
+            g.npoly = now * (size_t)D * (size_t)GD * (size_t)L; g.b2_first = b2first; g.b2_kd = b2kd; g.b2_D = GD; g.b2_w = bw;
             if ((rc = launch(g, "tunnel base2 crt_digits")) != ALCH_OK) return rc;
         } else {
             GenCall<W> g = gx;
@@ -3769,13 +3810,14 @@ static int do_tunnel_pow2(const alch_tunnel* t, alch_ring* rin, const void* in, 
     alch_ring* rs = t->rs;
     const int L = rs->L, dup = rr->L - rin->L, Lin = L - dup;
     const u32 d = t->d_rel;
-    const bool base2 = t->gadget == ALCH_GAD_BASE2, up = rs->n > rr->n, pin = (flags & ALCH_POW_IN) != 0;
+    const u32 bw = (u32)gadget_width(t->gadget);      // BaseBGad 2^bw; 0: TrivGad
+    const bool base2 = bw > 0, up = rs->n > rr->n, pin = (flags & ALCH_POW_IN) != 0;
     alch_ring* rd = up ? rr : rs;                      // the ring whose dimension the transforms run at
     const u32 n_d = rd->n;
     const bool c0_in_place = up && !pin;               // crt_S'(embed c0)[k] = crt_R'(c0)[k >> sh]: the input's CRT form serves as it is
     const u32 GD = base2 ? (u32)t->digits : (u32)Lin;  // digits per E'-coefficient
     Scal<u32> b2first, b2kd;
-    if (base2) base2_layout(rs, b2first, b2kd);
+    if (base2) base2_layout(rs, b2first, b2kd, bw);
     const size_t wb = sizeof(W), ebr = elem_bytes(rin), pd = (size_t)n_d * wb;        // pd: one limb-polynomial at the transforms' dimension
     const size_t x0_b = c0_in_place ? 0 : (size_t)d * Lin * pd, x1_b = base2 ? (size_t)d * L * pd : 0, dig_b = (size_t)d * GD * L * pd;
     const size_t per_ct = 2 * ebr + x0_b + x1_b + dig_b;
@@ -3816,16 +3858,15 @@ static int do_tunnel_pow2(const alch_tunnel* t, alch_ring* rin, const void* in, 
             nc.op = OP_CRT_BASE2; nc.ring = &dev_ring<W>(rd); nc.stream = rs->stream; nc.balanced = rd->balanced;
             nc.src = reinterpret_cast<const W*>(x1); nc.data = reinterpret_cast<W*>(dig);
             nc.npoly = now * (size_t)d * GD * (size_t)L;
-            nc.b2_first = b2first; nc.b2_kd = b2kd; nc.b2_D = GD;
+            nc.b2_first = b2first; nc.b2_kd = b2kd; nc.b2_D = GD; nc.b2_w = bw;
             if ((rc = launch(rd, nc, "tunnel crt_base2")) != ALCH_OK) return rc;
         } else {
             if (base2) {
                 const size_t elems = now * d;
                 for (size_t y0 = 0; y0 < elems; y0 += 32768) {             // grid.y is 16-bit
                     const unsigned ny = (unsigned)std::min<size_t>(32768, elems - y0);
-                    hipLaunchKernelGGL((k_decompose_base2<W>), dim3(ew_grid(elem_words(rd)), ny), dim3(256), 0, rs->stream, dev_ring<W>(rd),
-                                       reinterpret_cast<const W*>(x1) + y0 * elem_words(rd), reinterpret_cast<W*>(dig) + y0 * GD * elem_words(rd),
-                                       b2first, b2kd, GD);
+                    launch_decompose_baseb<W>(rd, rs->stream, dev_ring<W>(rd), ny, reinterpret_cast<const W*>(x1) + y0 * elem_words(rd),
+                                              reinterpret_cast<W*>(dig) + y0 * GD * elem_words(rd), b2first, b2kd, GD, bw);
                     HIP_TRY(hipGetLastError());
                 }
             }
@@ -4407,8 +4448,8 @@ static int ct_ks_hint(const char* name, bool whole, alch_buf* out, size_t out_fi
     BIND(r);
     if (v_crt->ring != r || err_crt->ring != r || sk_crt->ring != r)
         return fail(ALCH_E_INVALID, who + ": the values, the error terms and the key must belong to the output's ring");
-    if (gadget != ALCH_GAD_TRIV && gadget != ALCH_GAD_BASE2) return fail(ALCH_E_INVALID, who + ": unknown gadget");
-    const hintgad::Layout G = hintgad::make_layout(r->q, r->L, gadget == ALCH_GAD_BASE2);
+    if (gadget_width(gadget) < 0) return fail(ALCH_E_INVALID, who + ": unknown gadget");
+    const hintgad::Layout G = hintgad::make_layout_code(r->q, r->L, gadget);
     const size_t D = G.D;
     if (D == 0) return fail(ALCH_E_INVALID, who + ": the gadget has no entries on this ring");
     if (whole) {

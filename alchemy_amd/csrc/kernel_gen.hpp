@@ -96,6 +96,7 @@ struct GenCall {
     bool with_diag;            // GEN_CRT_DIGITS: also transform the digits i == j (tunnel: no CRT copy of the source exists)
     Scal<u32> b2_first, b2_kd; // GEN_CRT_BASE2: first digit and digit count of every limb
     u32 b2_D;                  // GEN_CRT_BASE2: digits per element
+    u32 b2_w = 1;              // GEN_CRT_BASE2: log2 of the base (1: BaseBGad 2)
     int src_limbs, src_first;  // GEN_CRT_DIGITS: the source elements hold limbs src_first .. src_first + src_limbs - 1 (0 = all L)
     u32 skip_mask;             // GEN_L .. GEN_DIVG_*: bit l set = leave prime-power factor l alone (tunnel: partial lInv)
     bool zdom;                 // the ring's "modulus" is 0: signed 64-bit integers (Pow / Dec operations only)
@@ -428,9 +429,10 @@ __global__ void __launch_bounds__(NT, 4) k_gen_crt_digits(DevRing<W> R, GenDev<W
 // binary digits have the closed form  d_t = -((u >> t) & 1)  for t < k - 1 and the top digit is  -(u >> (k - 1))  (arithmetic
 // shifts), so no digit depends on the ones below it and the digits never exist in HBM untransformed (k_crt_base2_digits is the
 // two-power form).  digits: [element][D][L][n].
-template <typename W, int NT = GEN_T>
+// P2: BaseBGad 2^gw, gw >= 2, by the closed form of hint_gadget.hpp (pow2_digit); every digit that can reach q_j is reduced.
+template <typename W, int NT = GEN_T, bool P2 = false>
 __global__ void __launch_bounds__(NT, 4) k_gen_crt_base2_digits(DevRing<W> R, GenDev<W> G, const W* __restrict__ xpow, W* __restrict__ digits,
-                                                                Scal<u32> first_digit, Scal<u32> kd, u32 D) {
+                                                                Scal<u32> first_digit, Scal<u32> kd, u32 D, u32 gw) {
     typedef typename Signed<W>::type SW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     W* lds = reinterpret_cast<W*>(smem);
@@ -447,12 +449,21 @@ __global__ void __launch_bounds__(NT, 4) k_gen_crt_base2_digits(DevRing<W> R, Ge
     const W* src = xpow + (el * (size_t)L + i) * (size_t)n;
     W* dst = digits + p * (size_t)n;
     const W q = R.mod[j].q, qni = R.mod[j].qni, qi = R.mod[i].q, hqi = (qi - 1) >> 1;
+    SW coff = 0;
+    bool wide = top;                                        // the digit may reach q_j: reduce it
+    if constexpr (P2) { coff = hintgad::pow2_offset<SW>(gw, t); wide = top || (q >> (gw - 1)) == 0; }
     for (u32 k = threadIdx.x; k < n; k += NT) {
         const W v = src[k];
         const SW z = v > hqi ? (SW)v - (SW)qi : (SW)v;
-        const SW u = -z;
-        SW dg = top ? -(u >> t) : -((u >> t) & 1);
-        if (top) dg %= (SW)q;                               // the top digit is tiny but its size depends on q_i vs 2^k
+        SW dg;
+        if constexpr (P2) {
+            dg = hintgad::pow2_digit<SW>(z, gw, t, top, coff);
+            if (wide) dg %= (SW)q;
+        } else {
+            const SW u = -z;
+            dg = top ? -(u >> t) : -((u >> t) & 1);
+            if (top) dg %= (SW)q;                           // the top digit is tiny but its size depends on q_i vs 2^k
+        }
         lds[k] = dg < 0 ? (W)(dg + (SW)q) : (W)dg;
     }
     lds_barrier();
@@ -1228,9 +1239,9 @@ inline hipError_t gen_run_nt(const GenCall<W>& c, size_t lds_bytes) {
         break;
     }
     case GEN_CRT_BASE2: {
-        auto k = k_gen_crt_base2_digits<W, NT>;
+        auto k = c.b2_w > 1 ? k_gen_crt_base2_digits<W, NT, true> : k_gen_crt_base2_digits<W, NT, false>;
         if ((e = set_lds(k, lds_bytes)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3((unsigned)c.npoly), dim3(NT), lds_bytes, c.stream, *c.ring, *c.gen, c.src, c.data, c.b2_first, c.b2_kd, c.b2_D);
+        hipLaunchKernelGGL(k, dim3((unsigned)c.npoly), dim3(NT), lds_bytes, c.stream, *c.ring, *c.gen, c.src, c.data, c.b2_first, c.b2_kd, c.b2_D, c.b2_w);
         break;
     }
     case GEN_CRT_DIGITS: {

@@ -120,7 +120,7 @@ __global__ void k_ct_encrypt(DevRing<W> R, W* out, const W* err, const W* sk, si
 
 // ---- key-switch and tunnel hints (ksHint, KeysHints.hs:101-129), ring arithmetic ---------------------------------------------
 // For value i and gadget entry t < D, e = i D + t: out[2e + 1] = a, uniform words by k_ct_encrypt's rule; out[2e] = g_t v[i] + err[e] - a s.
-// g_t is 2^d(t) on limb i(t) and 0 elsewhere (hint_gadget.hpp), so v is read on one limb of every entry only.  One launch serves the
+// g_t is 2^(w d(t)) on limb i(t) and 0 elsewhere (hint_gadget.hpp; w = 1 for BaseBGad 2, d = 0 for TrivGad), so v is read on one limb of every entry only.  One launch serves the
 // entries [e0, e0 + count): out, err and the counter ct0 are those of entry e0, v is value 0.  Walked as [i][t L + j][k] from the
 // position of entry e0: t and j come from one 32-bit division, i never needs a 64-bit one.  words = count L n.
 template <typename W, int VW>
@@ -139,7 +139,7 @@ __global__ void k_ct_ks_hint(DevRing<W> R, hintgad::Layout G, W* out, const W* v
         u32 gl, gd;
         hintgad::entry(G, t, gl, gd);
         if (gl == j) {
-            const W g = mont_mul((W)((W)1 << gd), m.r2, m);  // 2^d < q_j, to Montgomery form
+            const W g = mont_mul((W)((W)1 << (gd * G.w)), m.r2, m);  // 2^(w d) < q_j, to Montgomery form
             const P x = reinterpret_cast<const P*>(v)[(wk.outer * L + j) * nv + wk.k];
 #pragma unroll
             for (int c = 0; c < VW; ++c) h0.v[c] = add_mod(h0.v[c], mont_mul(x.v[c], g, m), m.q);

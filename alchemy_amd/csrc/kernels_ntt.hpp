@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "ntt_engine.hpp"
+#include "hint_gadget.hpp"
 
 namespace alch {
 
@@ -135,8 +136,9 @@ struct NttCall {
     void* stash;           // OP_RESCALE_OUT: Signed<W> [grid][ddn][n]
     unsigned stash_slots;
     bool pow_out;
-    Scal<u32> b2_first, b2_kd;   // OP_CRT_BASE2: BaseBGad 2 layout (first digit and digit count of every limb)
+    Scal<u32> b2_first, b2_kd;   // OP_CRT_BASE2: BaseBGad layout (first digit and digit count of every limb)
     u32 b2_D;
+    u32 b2_w = 1;                // OP_CRT_BASE2: log2 of the base (1: BaseBGad 2)
 };
 
 // ---- staging helpers -------------------------------------------------------------------------------
@@ -185,9 +187,12 @@ __global__ void __launch_bounds__(Geo<LOGN>::T) k_crt(DevRing<W> R, W* data, con
 // sizes): workgroup p = (ciphertext, digit d, target limb j).  Digit d is bit t of source limb i; with u = -(centred
 // lift of c2_i) the balanced binary digits have the closed form  d_t = -((u >> t) & 1)  for t < k - 1 and the top
 // digit is  -(u >> (k - 1))  (arithmetic shifts), so no digit depends on the ones below it.
-template <int LOGN, typename W>
+// P2: BaseBGad 2^gw, gw >= 2 -- digit d is digit t of source limb i in base 2^gw, by the closed form of hint_gadget.hpp
+// (pow2_digit); the top digit is reduced mod q_j as before, and so is every other digit when q_j < 2^(gw-1), because such a target
+// modulus is smaller than a non-top digit can be (`wide`, uniform over the workgroup).
+template <int LOGN, typename W, bool P2 = false>
 __global__ void __launch_bounds__(Geo<LOGN>::T) k_crt_base2_digits(DevRing<W> R, const W* __restrict__ c2pow, W* __restrict__ digits,
-                                                                   Scal<u32> first_digit, Scal<u32> kd, u32 D) {
+                                                                   Scal<u32> first_digit, Scal<u32> kd, u32 D, u32 gw) {
     typedef Geo<LOGN> G;
     typedef typename Vec4<W>::type V;
     typedef typename Signed<W>::type SW;
@@ -206,15 +211,24 @@ __global__ void __launch_bounds__(Geo<LOGN>::T) k_crt_base2_digits(DevRing<W> R,
     const W* src = c2pow + (ct * (size_t)L + i) * (size_t)G::N;
     W* dst = digits + p * (size_t)G::N;
     const W q = R.mod[j].q, qni = R.mod[j].qni, qi = R.mod[i].q, hqi = (qi - 1) >> 1;
+    SW coff = 0;
+    bool wide = top;                                        // the digit may reach q_j: reduce it
+    if constexpr (P2) { coff = hintgad::pow2_offset<SW>(gw, t); wide = top || (q >> (gw - 1)) == 0; }
     stage_in<LOGN, W>(lds, [&](int idx) {
         const V v = *reinterpret_cast<const V*>(src + idx);
         V o;
 #pragma unroll
         for (int e = 0; e < VL; ++e) {
             const SW z = v[e] > hqi ? (SW)v[e] - (SW)qi : (SW)v[e];
-            const SW u = -z;
-            SW dg = top ? -(u >> t) : -((u >> t) & 1);
-            if (top) { dg %= (SW)q; }                       // the top digit is tiny but its size depends on q_i vs 2^k
+            SW dg;
+            if constexpr (P2) {
+                dg = hintgad::pow2_digit<SW>(z, gw, t, top, coff);
+                if (wide) { dg %= (SW)q; }
+            } else {
+                const SW u = -z;
+                dg = top ? -(u >> t) : -((u >> t) & 1);
+                if (top) { dg %= (SW)q; }                   // the top digit is tiny but its size depends on q_i vs 2^k
+            }
             o[e] = dg < 0 ? (W)(dg + (SW)q) : (W)dg;
         }
         return o;
@@ -663,9 +677,9 @@ inline hipError_t run_call(const NttCall<W>& c) {
         break;
     }
     case OP_CRT_BASE2: {
-        auto k = k_crt_base2_digits<LOGN, W>;
+        auto k = c.b2_w > 1 ? k_crt_base2_digits<LOGN, W, true> : k_crt_base2_digits<LOGN, W, false>;
         if ((e = set_lds(k, lds_bytes)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3((unsigned)c.npoly), dim3(G::T), lds_bytes, c.stream, R, c.src, c.data, c.b2_first, c.b2_kd, c.b2_D);
+        hipLaunchKernelGGL(k, dim3((unsigned)c.npoly), dim3(G::T), lds_bytes, c.stream, R, c.src, c.data, c.b2_first, c.b2_kd, c.b2_D, c.b2_w);
         break;
     }
     case OP_RESCALE_OUT: {

@@ -17,6 +17,7 @@
 // (alch_ct_tunnel, alch_ct_mul_full, alch_ct_mod_switch, alch_buf_*), which carry the same (enc, k, l, p) metadata on the host.
 #pragma once
 #include "cycgen.hpp"
+#include "../csrc/hint_gadget.hpp"
 
 namespace alchemy {
 namespace gen {
@@ -204,15 +205,22 @@ inline CT operator*(const CT& a_, const CT& b_) {
 struct KSHint { std::vector<std::pair<Cyc, Cyc>> h; };          // one (b, a) per gadget entry, CRT basis; b + a s = g_t v + e
 
 // The gadget vector as per-limb scalars (Lol Gadget for an RNS product: the per-limb gadgets placed in their own limb, zeros
-// elsewhere): TrivGad = the unit vectors; BaseBGad 2 = 2^t on limb i for t < ceil(log2 q_i), limb 0's entries first.
+// elsewhere): TrivGad = the unit vectors; BaseBGad 2^w (ALCH_GAD_BASE2: w = 1; ALCH_GAD_BASEPOW2(w)) = 2^(w t) on limb i for
+// t < ceil(ceil(log2 q_i) / w), limb 0's entries first.
+inline int gadgetWidth(int gadget) {                              // 0: TrivGad; the library's own predicate (hint_gadget.hpp)
+    const int w = alch::hintgad::gadget_width(gadget);
+    if (w < 0) throw std::runtime_error("unknown gadget code");
+    return w;
+}
 inline std::vector<std::vector<uint64_t>> gadgetVector(const Ring& r, int gadget) {
     std::vector<std::vector<uint64_t>> g;
+    const int w = gadgetWidth(gadget);
     for (int i = 0; i < r.L(); ++i) {
         int k = 1;
-        if (gadget == ALCH_GAD_BASE2) { k = 0; for (uint64_t v = 1; v < r.qs()[i]; v <<= 1) ++k; }
+        if (w > 0) { k = 0; for (uint64_t v = 1; v < r.qs()[i]; v <<= 1) ++k; k = (k + w - 1) / w; }
         for (int t = 0; t < k; ++t) {
             std::vector<uint64_t> e(r.L(), 0);
-            e[i] = powmod(2, (uint64_t)t, r.qs()[i]);
+            e[i] = powmod(2, (uint64_t)(w * t), r.qs()[i]);
             g.push_back(e);
         }
     }
@@ -566,9 +574,8 @@ struct DevBufs {                                    // frees what it holds, in a
 };
 
 inline size_t gadgetDigits(const Ring& r, int gadget) {
-    if (gadget == ALCH_GAD_TRIV) return (size_t)r.L();
     int nd = 0;
-    check(alch_decompose_base2(r.handle(), nullptr, nullptr, &nd), "alch_decompose_base2");
+    check(alch_gadget_digits(r.handle(), gadget, &nd), "alch_gadget_digits");
     return (size_t)nd;
 }
 

@@ -18,11 +18,11 @@ def moduli(L):
     return list(reversed(QS[:L]))                                      # last-taken modulus outermost
 
 
-def limb_counts():
-    """[(L_in, L_hint, L_out)] of switch1 .. switch5 (host-only)."""
+def limb_counts(gadget=capi.ALCH_GAD_BASE2):
+    """[(L_in, L_hint, L_out)] of switch1 .. switch5 (host-only); gadget: the reference's BaseBGad 2 or ALCH_GAD_BASEPOW2(w)."""
     p, tuns = 0, []
     for _ in range(5):
-        lin, lh, lout, p = capi.select_limbs(QS, p, capi.ALCH_OP_TUNNEL, capi.ALCH_GAD_BASE2)
+        lin, lh, lout, p = capi.select_limbs(QS, p, capi.ALCH_OP_TUNNEL, gadget)
         tuns.append((lin, lh, lout))
     tuns.reverse()
     return tuns
@@ -31,19 +31,19 @@ def limb_counts():
 class Hop:
     """One hop H_k' -> H_k+1' with resident hint and a seeded input batch."""
 
-    def __init__(self, k, batch, ring_opts=()):
-        self.k, self.B = k, batch
-        self.lin, self.lh, self.lout = limb_counts()[k]
+    def __init__(self, k, batch, ring_opts=(), gadget=capi.ALCH_GAD_BASE2):
+        self.k, self.B, self.gadget = k, batch, gadget
+        self.lin, self.lh, self.lout = limb_counts(gadget)[k]
         self._rings = {}
         self.ring_opts = tuple(ring_opts)
         lin, lh, lout = self.lin, self.lh, self.lout
         self.rin, self.rr = self.ring(HP[k], lin), self.ring(HP[k], lh)
         self.rs, self.ro = self.ring(HP[k + 1], lh), self.ring(HP[k + 1], lout)
         _, self.d_rel = Tunnel.info(self.rr, self.rs)
-        self.D = self.rs.gadget_digits(capi.ALCH_GAD_BASE2)
+        self.D = self.rs.gadget_digits(gadget)
         self.lin_buf, self.ks = self.rs.alloc(self.d_rel), self.rs.alloc(2 * self.d_rel * self.D)
         self.lin_buf.fill_uniform(SEED_LIN); self.ks.fill_uniform(SEED_KS)
-        self.tun = Tunnel(self.rr, self.rs, self.lin_buf, self.ks, gadget=capi.ALCH_GAD_BASE2)
+        self.tun = Tunnel(self.rr, self.rs, self.lin_buf, self.ks, gadget=gadget)
         self.x = self.rin.alloc(2 * batch)
         self.x.fill_uniform(SEED_X)
         self.up = self.rr.alloc(2 * batch) if lh != lin else None

@@ -76,6 +76,9 @@ foreign import ccall safe   "alch_crt_set_dec"         c_crtSetDec       :: Word
 -- decompose + reduce (Gadget / Decompose instances of TrivGad and BaseBGad 2)
 foreign import ccall safe   "alch_decompose_triv"      c_decomposeTriv   :: Ptr AlchRing -> Ptr Int64 -> Ptr Int64 -> IO CInt
 foreign import ccall safe   "alch_decompose_base2"     c_decomposeBase2  :: Ptr AlchRing -> Ptr Int64 -> Ptr Int64 -> Ptr CInt -> IO CInt
+-- BaseBGad 2^w (gadget code 0x100 .|. w, 1 <= w <= 16): the digits of any BaseBGad code, and the entry count of any gadget code
+foreign import ccall safe   "alch_decompose_baseb"     c_decomposeBaseB  :: Ptr AlchRing -> CInt -> Ptr Int64 -> Ptr Int64 -> Ptr CInt -> IO CInt
+foreign import ccall unsafe "alch_gadget_digits"       c_gadgetDigits    :: Ptr AlchRing -> CInt -> Ptr CInt -> IO CInt
 
 -- device-resident batches
 foreign import ccall safe   "alch_buf_alloc"           c_bufAlloc        :: Ptr AlchRing -> CSize -> Ptr (Ptr AlchBuf) -> IO CInt

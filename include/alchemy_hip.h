@@ -79,6 +79,15 @@ typedef struct alch_tunnel alch_tunnel;
 /* gadgets (Crypto/Alchemy/Interpreter/PT2CT.hs:139-140) */
 #define ALCH_GAD_TRIV 0            /* TrivGad: one digit per limb, centred lift                 */
 #define ALCH_GAD_BASE2 1           /* BaseBGad 2: sum_i ceil(log2 q_i) digits; unfused device path */
+/* BaseBGad 2^w, 1 <= w <= 16 (added within 1.8): limb i has k_i = ceil(ceil(log2 q_i) / w) digits, the smallest k with 2^(w k) >= q_i;
+ * limb 0's digits first, least significant first; non-top digits in [-2^(w-1), 2^(w-1)), the top digit absorbs the rest (Lol's
+ * divModCent); gadget entry t of limb i is 2^(w t) on limb i and 0 elsewhere.  About 1/w of BaseBGad 2's digit transforms for w - 1
+ * more bits of hint noise.  Accepted wherever a gadget code is taken (alch_hint_load, alch_hint_from_buf, alch_tunnel_create,
+ * alch_ct_ks_hint, alch_ct_ks_hint_part, alch_select_limbs, alch_gadget_digits, alch_decompose_baseb); such a hint or tunnel runs the
+ * composed (unfused) device path of BaseBGad 2.  ALCH_GAD_BASEPOW2(1) means exactly ALCH_GAD_BASE2: same digit count, same words.
+ * w = 0, w > 16 and every other code: ALCH_E_INVALID.  The cap at 16 is a decision, not a limit of the arithmetic: above it a digit
+ * is within 2^15 of TrivGad's on a 31-bit limb. */
+#define ALCH_GAD_BASEPOW2(w) (0x100 | (w))
 
 const char *alch_last_error(void);
 /* Library/ABI version: (major<<16)|minor; the minor number goes up with every added capability (1.7: tunnels between two-power rings; 1.8: decrypt / error rates on resident batches).).
@@ -125,7 +134,11 @@ int alch_ring_destroy(alch_ring *ring);
  * and the pNoise its input must have (feed that to the operation before it: PT2CT resolves a circuit backwards).
  *   op ALCH_OP_MUL     mul_        (PT2CT.hs:160-177):  modSwitch . keySwitchQuad hint . modSwitch $ x * y
  *   op ALCH_OP_TUNNEL  linearCyc_  (PT2CT.hs:207-229):  modSwitch . tunnel hint . modSwitch
- * ALCH_E_INVALID when the list does not hold enough units (PT2CT's type error "You need more/bigger moduli!"). */
+ * ALCH_E_INVALID when the list does not hold enough units (PT2CT's type error "You need more/bigger moduli!").
+ * The hint's units: KSPNoise = p + KSAccumPNoise + 5 (Max32BitUnits) for TrivGad and + 0 for BaseBGad 2 are the reference's
+ * (PT2CT.hs:139-140), which defines no other gadget.  For ALCH_GAD_BASEPOW2(w) the rule is THIS LIBRARY'S OWN:
+ * + ceil((w - 1) / 6.1), the digit's extra w - 1 bits in 6.1-bit units.  It reproduces both: + 0 at w = 1, and a 30.5-bit digit
+ * gives Max32BitUnits = 5. */
 #define ALCH_OP_MUL 0
 #define ALCH_OP_TUNNEL 1
 int alch_select_limbs(const uint64_t *moduli, int n_moduli, int op, int gadget, int p_noise_out, int *L_in, int *L_hint,
@@ -204,6 +217,12 @@ int alch_decompose_triv(alch_ring *ring, const int64_t *c_pow, int64_t *digits);
  * least significant first, the top digit absorbing the remainder; digits of limb 0 first.  *n_digits receives
  * their number D = sum_i ceil(log2 q_i); `digits` must hold D ring elements (pass NULL to query D only). */
 int alch_decompose_base2(alch_ring *ring, const int64_t *c_pow, int64_t *digits, int *n_digits);
+/* The same for any BaseBGad code (ALCH_GAD_BASE2, ALCH_GAD_BASEPOW2(w)): D = sum_i ceil(ceil(log2 q_i) / w) digits by the rule next to
+ * the gadget defines.  ALCH_GAD_TRIV and unknown codes: ALCH_E_INVALID.  Added within 1.8; probe for the symbol. */
+int alch_decompose_baseb(alch_ring *ring, int gadget, const int64_t *c_pow, int64_t *digits, int *n_digits);
+/* Host-only: the number of gadget entries D of any gadget code on this ring (L for ALCH_GAD_TRIV).  ALCH_E_INVALID: null argument,
+ * unknown code.  Added within 1.8; probe for the symbol. */
+int alch_gadget_digits(const alch_ring *ring, int gadget, int *D);
 
 /* ---- device-resident ring-element arrays --------------------------------------------------------
  * What a Haskell `ForeignPtr`-wrapped tensor would hold; upload/download do the AoS <-> limb-major
@@ -633,7 +652,8 @@ int alch_ct_encrypt(alch_buf *out, size_t batch, const alch_buf *err_crt, size_t
  * ksHint (KeysHints.hs:101-129): for every value v_i and every gadget entry t an RLWE sample under the key with g_t v_i added.  The
  * gadget has D entries: D = L for ALCH_GAD_TRIV, D = sum_i ceil(log2 q_i) for ALCH_GAD_BASE2, the digits of limb 0 first, least
  * significant first (the order of alch_hint_load and alch_decompose_base2).  Entry t belongs to limb i(t) with exponent d(t) (0 for
- * TrivGad): g_t is 2^d(t) on limb i(t) and 0 on every other limb.  For i < n_v, t < D and e = i D + t, everything on the CRT basis of
+ * TrivGad): g_t is 2^d(t) on limb i(t) and 0 on every other limb.  ALCH_GAD_BASEPOW2(w): D = sum_i ceil(ceil(log2 q_i) / w) in the
+ * same order and g_t = 2^(w d(t)), which stays below q_i(t).  For i < n_v, t < D and e = i D + t, everything on the CRT basis of
  * one ring:
  *   out[out_first + 2e + 1] = a, word (limb j, slot k) = splitmix64(seed + ((2 (ct0 + e) + 1) L + j) n + k) mod q_j  (alch_ct_encrypt's
  *                             rule: ct0 cuts a long hint into chunks the same way)
