@@ -14,6 +14,7 @@ ALCH_E_INVALID, ALCH_E_NOT_PRIME, ALCH_E_NO_CRT, ALCH_E_UNSUPPORTED = -1, -2, -3
 ALCH_E_NO_DEVICE, ALCH_E_HIP, ALCH_E_NOMEM, ALCH_E_INTERNAL = -5, -6, -7, -8
 ALCH_POW_IN, ALCH_POW_OUT = 1, 2
 ALCH_GAD_TRIV, ALCH_GAD_BASE2 = 0, 1
+ALCH_RNG_SPLITMIX, ALCH_RNG_CHACHA20 = 0, 1
 
 
 def ALCH_GAD_BASEPOW2(w: int) -> int:
@@ -51,6 +52,7 @@ SYMBOLS = [
     "alch_gauss_table", "alch_gauss_plan", "alch_buf_gauss_dec", "alch_ct_encrypt",
     "alch_ct_ks_hint", "alch_ct_ks_hint_part",
     "alch_gadget_digits", "alch_decompose_baseb",
+    "alch_ring_set_rng_key", "alch_ring_rng", "alch_rng_words",
 ]
 
 
@@ -194,6 +196,9 @@ def load_library():
         "alch_ct_ks_hint": [VP, C.c_size_t, C.c_int, C.c_size_t, VP, C.c_size_t, VP, C.c_size_t, VP, C.c_size_t, C.c_uint64, C.c_uint64],
         "alch_ct_ks_hint_part": [VP, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, VP, C.c_size_t, VP, C.c_size_t, VP, C.c_size_t, C.c_uint64,
                                  C.c_uint64],
+        "alch_ring_set_rng_key": [VP, C.c_char_p],
+        "alch_ring_rng": [VP],
+        "alch_rng_words": [C.c_char_p, C.c_uint64, C.c_uint, C.c_uint64, C.c_size_t, PU64],
     }
     for name, args in sig.items():
         fn = getattr(l, name)
@@ -283,6 +288,21 @@ class Ring:
             self.close()
         except Exception:
             pass
+
+    # --- keyed streams for the samplers
+    def set_rng_key(self, key: bytes | None):
+        """32 key bytes: gauss_dec / ct_encrypt / ct_ks_hint that WRITE into this ring draw from ChaCha20 keystreams (key, seed, domain,
+        position); None goes back to splitmix64.  A (key, seed) pair serves one batch per entry point."""
+        if key is not None:
+            key = bytes(key)
+            if len(key) != 32:
+                raise ValueError("the key is 32 bytes")
+        _check(self._l.alch_ring_set_rng_key(self._h, key))
+
+    @property
+    def rng(self) -> int:
+        """ALCH_RNG_SPLITMIX (0) or ALCH_RNG_CHACHA20 (1)."""
+        return _check(self._l.alch_ring_rng(self._h))
 
     # --- stream / timing
     def set_stream(self, hip_stream: int):

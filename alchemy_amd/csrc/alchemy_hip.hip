@@ -22,6 +22,7 @@
 #include "ring_host.hpp"
 #include "gen_host.hpp"
 #include "plain_host.hpp"
+#include "chacha_stream.hpp"
 
 using namespace alch;
 
@@ -90,6 +91,8 @@ struct alch_ring {
     size_t ws_maxd_bytes = 0;
     void* ws_gauss = nullptr;                  // alch_buf_gauss_dec on an index with odd primes: the doubles of one chunk of elements
     size_t ws_gauss_bytes = 0;
+    bool rng_keyed = false;                    // alch_ring_set_rng_key: the samplers that write into this ring draw from ChaCha20 keystreams
+    chacha::Key rng_key = {{0}};               // host copy only: it reaches the kernels by value, zeroed on reset and on destroy
     int device = 0;                            // HIP device the ring's streams, tables and buffers live on
     LaunchOpts opts;                           // launch-structure options (alch_ring_set_option)
     bool one_stream = false;
@@ -1613,6 +1616,12 @@ static int ring_create_impl(uint32_t m, int L, const uint64_t* q, bool nocrt, al
 extern "C" int alch_ring_create(uint32_t m, int L, const uint64_t* q, alch_ring** out) try { return ring_create_impl(m, L, q, false, out); } catch (...) { return abi_catch(); }
 extern "C" int alch_ring_create_nocrt(uint32_t m, int L, const uint64_t* q, alch_ring** out) try { return ring_create_impl(m, L, q, true, out); } catch (...) { return abi_catch(); }
 
+static void wipe_rng_key(alch_ring* r) {
+    volatile uint32_t* k = r->rng_key.k;           // volatile: the stores stay although the object dies next
+    for (int i = 0; i < 8; ++i) k[i] = 0;
+    r->rng_keyed = false;
+}
+
 extern "C" int alch_ring_destroy(alch_ring* r) try {
     if (!r) return ALCH_OK;
     ALCH_DEVICE_LOCK(r->device);
@@ -1652,7 +1661,41 @@ extern "C" int alch_ring_destroy(alch_ring* r) try {
         if (r->ev_xs[e]) (void)hipEventDestroy(r->ev_xs[e]);
     }
     r->stream_owner.reset();                       // destroys the stream with its last user
+    wipe_rng_key(r);
     delete r;
+    return ALCH_OK;
+} catch (...) { return abi_catch(); }
+
+// The 32 key bytes (NULL: back to splitmix64), copied under the device lock: a sampler call in flight on another thread has either the
+// old key or the new one, never a mixture.
+extern "C" int alch_ring_set_rng_key(alch_ring* r, const void* key) try {
+    if (!r) return fail(ALCH_E_INVALID, "null ring");
+    ALCH_DEVICE_LOCK(r->device);
+    wipe_rng_key(r);
+    if (key) { r->rng_key = chacha::load_key(static_cast<const uint8_t*>(key)); r->rng_keyed = true; }
+    return ALCH_OK;
+} catch (...) { return abi_catch(); }
+
+extern "C" int alch_ring_rng(const alch_ring* r) try {
+    if (!r) return fail(ALCH_E_INVALID, "null ring");
+    return r->rng_keyed ? ALCH_RNG_CHACHA20 : ALCH_RNG_SPLITMIX;
+} catch (...) { return abi_catch(); }
+
+// The definition made callable (host only): the pairs (A, B) of positions x0 .. x0 + count - 1 of (key, nonce, domain).
+extern "C" int alch_rng_words(const void* key, uint64_t nonce, unsigned domain, uint64_t x0, size_t count, uint64_t* out) try {
+    if (!key || (!out && count)) return fail(ALCH_E_INVALID, "alch_rng_words: null pointer");
+    if (domain >= chacha::DOMAINS) return fail(ALCH_E_INVALID, "alch_rng_words: the domain is a tag below 256");
+    if (!chacha::range_ok(x0, count)) return fail(ALCH_E_INVALID, "alch_rng_words: positions end at 2^58");
+    const chacha::Key K = chacha::load_key(static_cast<const uint8_t*>(key));
+    u64 u[8];
+    for (size_t i = 0; i < count; ++i) {
+        const u64 x = x0 + i;
+        if (i == 0 || chacha::slot(x) == 0) chacha::block(K, chacha::block_counter(domain, x), nonce, u);
+        out[2 * i] = u[2 * chacha::slot(x)];
+        out[2 * i + 1] = u[2 * chacha::slot(x) + 1];
+    }
+    volatile u64* w = u;                           // keystream of the caller's key: not left on the stack
+    for (int i = 0; i < 8; ++i) w[i] = 0;
     return ALCH_OK;
 } catch (...) { return abi_catch(); }
 
@@ -4320,6 +4363,9 @@ static void launch_gauss_axis(hipStream_t st, const gauss::Axis& a, double* xs, 
     }
 }
 
+// Keystream blocks that meet the positions [ctr0, ctr0 + total), total >= 1: the lanes of a keyed Gaussian launch.
+static inline size_t keyed_blocks(u64 ctr0, size_t total) { return (size_t)(((ctr0 + total - 1) >> 2) - (ctr0 >> 2) + 1); }
+
 // `count` elements at dst (limb-major words of r), coset: the Z_p words of the first element or null.
 template <typename W>
 static int do_gauss_dec(alch_ring* r, const gauss::Plan& P, void* dst, size_t count, u32 p, const u32* coset, uint64_t seed, uint64_t elem0) {
@@ -4332,8 +4378,14 @@ static int do_gauss_dec(alch_ring* r, const gauss::Plan& P, void* dst, size_t co
         while (((u32)1 << G.logn) < r->n) ++G.logn;
         G.ctr0 = elem0 * (u64)n;
         const size_t total = count * n;
-        hipLaunchKernelGGL((k_gauss_sample<W, true>), dim3(ew_grid(total)), dim3(256), 0, r->stream, G, (double*)nullptr,
-                           reinterpret_cast<W*>(dst), coset, total);
+        if (r->rng_keyed) {
+            const size_t blocks = keyed_blocks(G.ctr0, total);
+            hipLaunchKernelGGL((k_gauss_sample_keyed<W, true>), dim3(ew_grid(blocks)), dim3(256), 0, r->stream, G, r->rng_key,
+                               (double*)nullptr, reinterpret_cast<W*>(dst), coset, total, blocks);
+        } else {
+            hipLaunchKernelGGL((k_gauss_sample<W, true>), dim3(ew_grid(total)), dim3(256), 0, r->stream, G, (double*)nullptr,
+                               reinterpret_cast<W*>(dst), coset, total);
+        }
         HIP_TRY(hipGetLastError());
         return ALCH_OK;
     }
@@ -4345,8 +4397,14 @@ static int do_gauss_dec(alch_ring* r, const gauss::Plan& P, void* dst, size_t co
         const size_t now = std::min(chunk, count - done);
         const u32 total = (u32)(now * n);
         G.ctr0 = (elem0 + (u64)done) * (u64)n;
-        hipLaunchKernelGGL((k_gauss_sample<W, false>), dim3(ew_grid(total)), dim3(256), 0, r->stream, G, xs, (W*)nullptr,
-                           (const u32*)nullptr, (size_t)total);
+        if (r->rng_keyed) {
+            const size_t blocks = keyed_blocks(G.ctr0, total);
+            hipLaunchKernelGGL((k_gauss_sample_keyed<W, false>), dim3(ew_grid(blocks)), dim3(256), 0, r->stream, G, r->rng_key, xs,
+                               (W*)nullptr, (const u32*)nullptr, (size_t)total, blocks);
+        } else {
+            hipLaunchKernelGGL((k_gauss_sample<W, false>), dim3(ew_grid(total)), dim3(256), 0, r->stream, G, xs, (W*)nullptr,
+                               (const u32*)nullptr, (size_t)total);
+        }
         for (const gauss::Axis& a : P.axes) launch_gauss_axis(r->stream, a, xs, r->n, total / (a.p - 1));
         hipLaunchKernelGGL((k_gauss_round<W>), dim3(ew_grid(total)), dim3(256), 0, r->stream, G, xs,
                            reinterpret_cast<W*>(dst) + done * elem_words(r), coset ? coset + done * n : nullptr, total);
@@ -4378,6 +4436,8 @@ extern "C" int alch_buf_gauss_dec(alch_buf* dst, size_t first, size_t count, uin
     for (const gauss::Axis& a : P.axes)
         if (a.p > gauss::MAX_ODD_PRIME) return fail(ALCH_E_UNSUPPORTED, "alch_buf_gauss_dec: odd primes of the index up to 13 are served");
     if (!gauss::bound_ok(P, p)) return fail(ALCH_E_INVALID, "alch_buf_gauss_dec: svar is too large: the rounded coefficients would not stay below 2^62");
+    if (r->rng_keyed && !chacha::range_ok((unsigned __int128)elem0 * r->n, (unsigned __int128)count * r->n))
+        return fail(ALCH_E_INVALID, "alch_buf_gauss_dec: under a key the positions (elem0 + count) n end at 2^58");
     if (count == 0) return ALCH_OK;
     char* d = reinterpret_cast<char*>(dst->dptr) + first * elem_bytes(r);
     const u32* cs = nullptr;
@@ -4401,7 +4461,12 @@ static int do_ct_encrypt(alch_ring* r, void* out, size_t batch, const void* err,
     const size_t words = batch * elem_words(r);
     W* o = reinterpret_cast<W*>(out);
     const W *e = reinterpret_cast<const W*>(err), *s = reinterpret_cast<const W*>(sk);
-    ALCH_LAUNCH_VW(k_ct_encrypt, r, words, r->stream, R, o, e, s, words, seed, ct0);
+    if (r->rng_keyed) {                                      // a block per pack of four words when n allows, else a block per word
+        if (r->n % 4 == 0) hipLaunchKernelGGL((k_ct_encrypt_keyed<W, 4>), dim3(ew_grid(words / 4)), dim3(256), 0, r->stream, R, r->rng_key, o, e, s, words, seed, ct0);
+        else hipLaunchKernelGGL((k_ct_encrypt_keyed<W, 1>), dim3(ew_grid(words)), dim3(256), 0, r->stream, R, r->rng_key, o, e, s, words, seed, ct0);
+    } else {
+        ALCH_LAUNCH_VW(k_ct_encrypt, r, words, r->stream, R, o, e, s, words, seed, ct0);
+    }
     HIP_TRY(hipGetLastError());
     return ALCH_OK;
 }
@@ -4416,6 +4481,8 @@ extern "C" int alch_ct_encrypt(alch_buf* out, size_t batch, const alch_buf* err_
     if (!range_ok(err_first, batch, err_crt->n_elems)) return fail(ALCH_E_INVALID, "alch_ct_encrypt: error-term range out of bounds");
     if (sk_index >= sk_crt->n_elems) return fail(ALCH_E_INVALID, "alch_ct_encrypt: key index out of bounds");
     if (!r->has_crt) return fail(ALCH_E_NO_CRT, "alch_ct_encrypt: this ring has no CRT basis (created with alch_ring_create_nocrt)");
+    if (r->rng_keyed && chacha::odd_pos_end((unsigned __int128)ct0 + batch, (u32)r->L, r->n) > chacha::X_END)
+        return fail(ALCH_E_INVALID, "alch_ct_encrypt: under a key the positions 2 (ct0 + batch) L n end at 2^58");
     if (batch == 0) return ALCH_OK;
     const size_t eb = elem_bytes(r);
     const void* e = reinterpret_cast<const char*>(err_crt->dptr) + err_first * eb;
@@ -4432,7 +4499,12 @@ static int do_ct_ks_hint(alch_ring* r, const hintgad::Layout& G, void* out, size
     const size_t words = e_count * elem_words(r);
     W* o = reinterpret_cast<W*>(out);
     const W *x = reinterpret_cast<const W*>(v), *e = reinterpret_cast<const W*>(err), *s = reinterpret_cast<const W*>(sk);
-    ALCH_LAUNCH_VW(k_ct_ks_hint, r, words, r->stream, R, G, o, x, e, s, words, (u64)e_first, seed, ct0);
+    if (r->rng_keyed) {
+        if (r->n % 4 == 0) hipLaunchKernelGGL((k_ct_ks_hint_keyed<W, 4>), dim3(ew_grid(words / 4)), dim3(256), 0, r->stream, R, r->rng_key, G, o, x, e, s, words, (u64)e_first, seed, ct0);
+        else hipLaunchKernelGGL((k_ct_ks_hint_keyed<W, 1>), dim3(ew_grid(words)), dim3(256), 0, r->stream, R, r->rng_key, G, o, x, e, s, words, (u64)e_first, seed, ct0);
+    } else {
+        ALCH_LAUNCH_VW(k_ct_ks_hint, r, words, r->stream, R, G, o, x, e, s, words, (u64)e_first, seed, ct0);
+    }
     HIP_TRY(hipGetLastError());
     return ALCH_OK;
 }
@@ -4465,6 +4537,8 @@ static int ct_ks_hint(const char* name, bool whole, alch_buf* out, size_t out_fi
     if (!range_ok(err_first, e_count, err_crt->n_elems)) return fail(ALCH_E_INVALID, who + ": error-term range out of bounds");
     if (sk_index >= sk_crt->n_elems) return fail(ALCH_E_INVALID, who + ": key index out of bounds");
     if (!r->has_crt) return fail(ALCH_E_NO_CRT, who + ": this ring has no CRT basis (created with alch_ring_create_nocrt)");
+    if (r->rng_keyed && chacha::odd_pos_end((unsigned __int128)ct0 + e_count, (u32)r->L, r->n) > chacha::X_END)
+        return fail(ALCH_E_INVALID, who + ": under a key the positions 2 (ct0 + entries) L n end at 2^58");
     if (e_count == 0) return ALCH_OK;
     const size_t eb = elem_bytes(r);
     void* o = reinterpret_cast<char*>(out->dptr) + out_first * eb;

@@ -7,7 +7,8 @@
 // axes of the index with every product and every sum rounded on its own (no fused multiply-add anywhere), one rounding.
 //
 // QUALITY.  The generator is splitmix64 on a counter: a STATISTICAL generator, not a cryptographic one, like the std::mt19937_64 of the
-// host path it stands beside.  Nothing here is fit to protect real data.
+// host path it stands beside.  Nothing here is fit to protect real data -- a ring with a key (alch_ring_set_rng_key) replaces the two
+// words of a coefficient by a pair of a ChaCha20 keystream (chacha_stream.hpp); everything behind the words stays.
 #pragma once
 
 #include <algorithm>
@@ -173,11 +174,17 @@ inline double z_bound(const Plan& P, uint32_t p) {
 }
 inline bool bound_ok(const Plan& P, uint32_t p) { const double b = z_bound(P, p); return std::isfinite(b) && b < 4611686018427387904.0; }
 
-// Element `elem` of the stream: n integers z (Dec basis).  coset: n words in [0, p), or null with p = 0 (errorRounded).
-inline void element(const Plan& P, uint64_t seed, uint64_t elem, uint32_t p, const uint32_t* coset, int64_t* z) {
+// Element `elem`: n integers z (Dec basis), the two words of coefficient c = elem n + i from words(c, w0, w1).  coset: n words in
+// [0, p), or null with p = 0 (errorRounded).
+template <typename F>
+inline void element_from(const Plan& P, F&& words, uint64_t elem, uint32_t p, const uint32_t* coset, int64_t* z) {
     const uint32_t n = P.n;
     std::vector<double> x(n);
-    for (uint32_t i = 0; i < n; ++i) x[i] = sample(seed, elem * (uint64_t)n + i, P.scale, CDT);
+    for (uint32_t i = 0; i < n; ++i) {
+        uint64_t w0, w1;
+        words(elem * (uint64_t)n + i, w0, w1);
+        x[i] = rn_mul((double)deviate(w0, w1, CDT), P.scale);
+    }
     for (const Axis& a : P.axes) {
         const uint32_t h = a.p - 1, dim = h * a.mp;
         std::vector<double> cv(h);
@@ -192,6 +199,12 @@ inline void element(const Plan& P, uint64_t seed, uint64_t elem, uint32_t p, con
         }
     }
     for (uint32_t i = 0; i < n; ++i) z[i] = round_coset(x[i], p, coset ? coset[i] : 0u);
+}
+
+// Element `elem` of the splitmix64 stream `seed`.
+inline void element(const Plan& P, uint64_t seed, uint64_t elem, uint32_t p, const uint32_t* coset, int64_t* z) {
+    element_from(P, [seed](uint64_t c, uint64_t& w0, uint64_t& w1) { w0 = mix64(seed + 2 * c); w1 = mix64(seed + 2 * c + 1); }, elem, p,
+                 coset, z);
 }
 
 }  // namespace gauss

@@ -2,7 +2,9 @@
 alch_ct_encrypt; host-only alch_gauss_table, alch_gauss_plan) -- the mirror image of decrypt.py.
 
 The error sampler is counter-based: every stored word is an integer-exact function of (seed, position), so a batch cut into chunks
-gives the words of one call.  splitmix64 is a statistical generator, not a cryptographic one."""
+gives the words of one call.  splitmix64 is a statistical generator, not a cryptographic one: for real secrets set a key on the ring that
+is written (Ring.set_rng_key) -- the same calls then draw from ChaCha20 keystreams addressed by (key, seed, domain, position), and a
+(key, seed) pair serves one batch per entry point."""
 from __future__ import annotations
 
 import ctypes as C

@@ -3,7 +3,7 @@ alch_ct_ks_hint, alch_ct_ks_hint_part) -- ksHint, ksQuadCircHint and tunnelHint 
 
 Seeds follow encrypt_batch: the Gaussian stream is splitmix64(seed), the uniform stream splitmix64(seed + 1).  Every stored word is an
 integer-exact function of (seed, position), so a hint made in chunks has the words of one call.  splitmix64 is a statistical
-generator, not a cryptographic one."""
+generator, not a cryptographic one; with a key on the ring (Ring.set_rng_key) both streams are ChaCha20 keystreams and the seeds are nonces."""
 from __future__ import annotations
 
 import ctypes as C

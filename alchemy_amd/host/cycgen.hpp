@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "../../include/alchemy_hip.h"
+#include "../csrc/chacha_stream.hpp"
 #include "../csrc/gauss_sampler.hpp"
 
 namespace alchemy {
@@ -96,6 +97,8 @@ public:
     bool hasCRT() const { return crt_; }
     const std::vector<uint64_t>& qs() const { return qs_; }
     size_t words() const { return (size_t)n_ * qs_.size(); }
+    // 32 key bytes (null: back to splitmix64): the device samplers that write into this ring draw from ChaCha20 keystreams
+    void setRngKey(const uint8_t* key) const { check(alch_ring_set_rng_key(h_, key), "alch_ring_set_rng_key"); }
 
 private:
     uint32_t m_, n_ = 0;
@@ -112,6 +115,7 @@ public:
         auto it = rings_.find(key);
         if (it == rings_.end()) {
             it = rings_.emplace(key, std::unique_ptr<Ring>(new Ring(m, qs, crt))).first;
+            if (keyed_) it->second->setRngKey(rng_key_);
             // one Tensor call at a time: all rings queue on one stream, so calls between two rings need no events
             if (!first_) first_ = it->second.get();
             else check(alch_ring_share_stream(it->second->handle(), first_->handle()), "alch_ring_share_stream");
@@ -119,9 +123,19 @@ public:
         return *it->second;
     }
 
+    // One key for every ring of the cache, those made later included (null: none).  The caller keeps (key, seed) pairs apart.
+    void setRngKey(const uint8_t* key) {
+        keyed_ = key != nullptr;
+        for (int i = 0; i < 32; ++i) rng_key_[i] = key ? key[i] : 0;
+        for (auto& kv : rings_) kv.second->setRngKey(key);
+    }
+    ~RingCache() { volatile uint8_t* k = rng_key_; for (int i = 0; i < 32; ++i) k[i] = 0; }
+
 private:
     std::map<std::tuple<uint32_t, std::vector<uint64_t>, bool>, std::unique_ptr<Ring>> rings_;
     const Ring* first_ = nullptr;
+    bool keyed_ = false;
+    uint8_t rng_key_[32] = {0};
 };
 
 enum class Basis { Pow, Dec, CRT };
@@ -561,8 +575,10 @@ inline std::vector<int64_t> errorCosetDec(uint32_t m, double svar, int64_t p, co
 // basis.  p = 0: errorRounded; else errorCoset into coset + p R (coset: phi(m) residues in [0, p), p < 2^31), svar the caller's (encrypt
 // passes svar * p^2, as errorCosetDec does).  A statistical generator like the mt19937_64 above, and a different stream: the two
 // samplers agree in distribution, not in values.
+// key (nullable): the 32 bytes of alch_ring_set_rng_key -- the words of coefficient c are then the pair of position c, domain 1, of the
+// ChaCha20 stream (key, nonce = seed), and (elem + 1) phi(m) must stay within 2^58.
 inline std::vector<int64_t> gaussDecCounter(uint32_t m, double svar, uint64_t seed, uint64_t elem, int64_t p = 0,
-                                            const std::vector<int64_t>* coset = nullptr) {
+                                            const std::vector<int64_t>* coset = nullptr, const uint8_t* key = nullptr) {
     if (!alch::gauss::svar_ok(svar)) throw std::runtime_error("gaussDecCounter: svar must be finite and positive");
     if (p < 0 || p >= ((int64_t)1 << 31) || (p != 0) != (coset != nullptr)) throw std::runtime_error("gaussDecCounter: bad coset");
     const alch::gauss::Plan P = alch::gauss::make_plan(m, svar);
@@ -573,7 +589,14 @@ inline std::vector<int64_t> gaussDecCounter(uint32_t m, double svar, uint64_t se
         for (int64_t v : *coset) cw.push_back((uint32_t)(((v % p) + p) % p));
     }
     std::vector<int64_t> z(P.n);
-    alch::gauss::element(P, seed, elem, (uint32_t)p, coset ? cw.data() : nullptr, z.data());
+    if (!key) {
+        alch::gauss::element(P, seed, elem, (uint32_t)p, coset ? cw.data() : nullptr, z.data());
+        return z;
+    }
+    if (!alch::chacha::range_ok((unsigned __int128)elem * P.n, P.n)) throw std::runtime_error("gaussDecCounter: keyed positions end at 2^58");
+    const alch::chacha::Key K = alch::chacha::load_key(key);
+    alch::gauss::element_from(P, [&K, seed](uint64_t c, uint64_t& w0, uint64_t& w1) { alch::chacha::pair(K, seed, alch::chacha::DOM_GAUSS, c, w0, w1); },
+                              elem, (uint32_t)p, coset ? cw.data() : nullptr, z.data());
     return z;
 }
 

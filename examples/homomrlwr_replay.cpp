@@ -14,7 +14,9 @@
 //
 //   homomrlwr_replay [batch] [--seed N] [--dump DIR] [--per-element] [--per-element-resident] [--per-element-zip-host]
 //                    [--host-mode buffers|resident] [--var-scale F] [--quiet-stages] [--device-decrypt] [--device-plaintext] [--device-encrypt]
-//                    [--device-hints]
+//                    [--device-hints] [--rng-key <64 hex digits>]
+// --rng-key sets one 256-bit key on every ring (alch_ring_set_rng_key): the device samplers of --device-encrypt / --device-hints then draw
+// from ChaCha20 keystreams; the host paths keep their mt19937_64.
 // --device-hints builds the five tunnel hints and the four quadratic hints on resident buffers -- tunnelHintDevice / ksQuadCircHintDevice
 // over alch_buf_gauss_dec, l / crt and alch_ct_ks_hint, the counter-based streams seeded from --seed, the genSK keys uploaded once per
 // ring -- instead of one gadget entry at a time on the host; every later line is the same.  Not with the --per-element* flags, which
@@ -69,6 +71,8 @@ int main(int argc, char** argv) {
     std::string dump;
     bool per_element = false, per_resident = false, per_ziphost = false, quiet = false, device_decrypt = false, device_plaintext = false, device_encrypt = false, device_hints = false;
     double var_scale = 1.0;
+    bool have_key = false;
+    uint8_t rng_key[32] = {0};
     Mode host_mode = Mode::Resident;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--seed") && i + 1 < argc) seed = strtoull(argv[++i], nullptr, 10);
@@ -81,6 +85,12 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--device-plaintext")) device_plaintext = true;
         else if (!strcmp(argv[i], "--device-encrypt")) device_encrypt = true;
         else if (!strcmp(argv[i], "--device-hints")) device_hints = true;
+        else if (!strcmp(argv[i], "--rng-key") && i + 1 < argc) {
+            const char* h = argv[++i];
+            have_key = strlen(h) == 64 && strspn(h, "0123456789abcdefABCDEF") == 64;
+            if (!have_key) { fprintf(stderr, "error: --rng-key takes 64 hex digits\n"); return 2; }
+            for (int k = 0; k < 32; ++k) { const char d[3] = {h[2 * k], h[2 * k + 1], 0}; rng_key[k] = (uint8_t)strtoul(d, nullptr, 16); }
+        }
         else if (!strcmp(argv[i], "--var-scale") && i + 1 < argc) var_scale = atof(argv[++i]);
         else if (!strcmp(argv[i], "--host-mode") && i + 1 < argc) host_mode = !strcmp(argv[++i], "buffers") ? Mode::HostBuffers : Mode::Resident;
         else B = (size_t)atoi(argv[i]);
@@ -94,6 +104,11 @@ int main(int argc, char** argv) {
     try {
         std::mt19937_64 rng(seed);
         RingCache rc;
+        if (have_key) {                                              // the device samplers of every ring draw from ChaCha20 keystreams
+            rc.setRngKey(rng_key);
+            printf("rng: ChaCha20 keystreams under --rng-key for the device samplers%s\n",
+                   device_encrypt || device_hints ? "" : " (none runs: add --device-encrypt / --device-hints)");
+        }
         PtOps ops(rc, {QS[4], QS[5]});
         // ---- PT2CT's limb counts, resolved backwards from the output pNoise 0
         Limbs muls[4], tuns[5];

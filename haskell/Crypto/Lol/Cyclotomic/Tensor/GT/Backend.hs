@@ -162,3 +162,7 @@ foreign import ccall safe   "alch_ct_encrypt"          c_ctEncrypt       :: Ptr 
 -- or in parts
 foreign import ccall safe   "alch_ct_ks_hint"          c_ctKsHint        :: Ptr AlchBuf -> CSize -> CInt -> CSize -> Ptr AlchBuf -> CSize -> Ptr AlchBuf -> CSize -> Ptr AlchBuf -> CSize -> Word64 -> Word64 -> IO CInt
 foreign import ccall safe   "alch_ct_ks_hint_part"     c_ctKsHintPart    :: Ptr AlchBuf -> CSize -> CInt -> CSize -> CSize -> Ptr AlchBuf -> CSize -> Ptr AlchBuf -> CSize -> Ptr AlchBuf -> CSize -> Word64 -> Word64 -> IO CInt
+-- keyed ChaCha20 streams for the samplers (include/alchemy_hip.h, "keyed streams"): the key is 32 bytes behind the pointer
+foreign import ccall safe   "alch_ring_set_rng_key"    c_ringSetRngKey   :: Ptr AlchRing -> Ptr () -> IO CInt
+foreign import ccall unsafe "alch_ring_rng"            c_ringRng         :: Ptr AlchRing -> IO CInt
+foreign import ccall safe   "alch_rng_words"           c_rngWords        :: Ptr () -> Word64 -> CUInt -> Word64 -> CSize -> Ptr Word64 -> IO CInt

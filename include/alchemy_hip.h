@@ -267,7 +267,8 @@ int alch_ring_device(const alch_ring *ring, int *device, void **hip_stream);
 int alch_buf_upload(alch_buf *buf, size_t first, size_t count, const int64_t *host);
 int alch_buf_download(const alch_buf *buf, size_t first, size_t count, int64_t *host);
 /* Synthetic residues: word (e,j,k) = splitmix64(seed + ((e*L + j)*n + k)) mod q_j  (oracle:
- * orc_fill_uniform uses the same rule). */
+ * orc_fill_uniform uses the same rule).  It fills TEST DATA, not secrets: it stays splitmix64 whatever the ring's key
+ * (alch_ring_set_rng_key), and under a key the odd elements it writes are no longer the c1 of alch_ct_encrypt. */
 int alch_buf_fill_uniform(alch_buf *buf, uint64_t seed);
 /* Batched Tensor crt / crtInv / pointwise ops on elements [first, first+count). */
 int alch_buf_crt(alch_buf *buf, size_t first, size_t count);
@@ -621,7 +622,8 @@ int alch_buf_add_bcast(alch_buf *dst, const alch_buf *src, const alch_buf *one, 
  *              cycgen.hpp), s = 0.0; s = s + Lc[i][k] * col[k] for k = 0 .. i, every product and every sum rounded on its own
  *   round      R(x) = sign(x) floor(|x| + 0.5); errorRounded: z = R(x); errorCoset with coset word v mod p: c = v centred,
  *              z = c + p R((x - c) / p); the stored word of limb j is z mod q_j, on the DECODING basis
- * splitmix64 is a STATISTICAL generator, not a cryptographic one -- like the mt19937_64 of the host path it stands beside.
+ * splitmix64 is a STATISTICAL generator, not a cryptographic one -- like the mt19937_64 of the host path it stands beside.  A ring
+ * with a key (alch_ring_set_rng_key, "keyed streams" below) takes w0, w1 from a ChaCha20 keystream instead.
  * Doubles cross the ABI as their IEEE-754 bit patterns in uint64_t. */
 /* Host only (no device needed).  cdt = NULL: *len = the table's length; else *len >= that on entry, the table is copied. */
 int alch_gauss_table(uint64_t *cdt, size_t *len);
@@ -642,7 +644,8 @@ int alch_buf_gauss_dec(alch_buf *dst, size_t first, size_t count, uint64_t svar_
                        uint64_t seed, uint64_t elem0);
 /* out[2b] = err_crt[err_first + b] - c1 * sk_crt[sk_index], out[2b + 1] = c1, b < batch: `CT LSD 0 1 [c0, c1]`, everything on the CRT
  * basis of one ring.  Word (b, limb j, slot k) of c1 is splitmix64(seed + ((2 (ct0 + b) + 1) L + j) n + k) mod q_j: with ct0 = 0 the
- * words alch_buf_fill_uniform(out, seed) puts into the odd elements; ct0 shifts the ciphertext counter as elem0 does above.
+ * words alch_buf_fill_uniform(out, seed) puts into the odd elements; ct0 shifts the ciphertext counter as elem0 does above.  A ring
+ * with a key (alch_ring_set_rng_key) draws c1 from a ChaCha20 keystream, and then also refuses positions that would reach 2^58.
  * batch = 0: ALCH_OK, nothing queued.  ALCH_E_INVALID: null buffer; buffers of different rings; out smaller than 2 * batch; a range or
  * the key index outside its buffer; out overlapping err_crt's range or the key.  ALCH_E_NO_CRT: a ring without CRT basis. */
 int alch_ct_encrypt(alch_buf *out, size_t batch, const alch_buf *err_crt, size_t err_first, const alch_buf *sk_crt, size_t sk_index,
@@ -659,7 +662,8 @@ int alch_ct_encrypt(alch_buf *out, size_t batch, const alch_buf *err_crt, size_t
  *                             rule: ct0 cuts a long hint into chunks the same way)
  *   out[out_first + 2e]     = g_t v_crt[v_first + i] + err_crt[err_first + e] - a * sk_crt[sk_index]
  * n_v = 1 gives the layout of alch_hint_from_buf (h0_0, h1_0, h0_1, ...), n_v = d_rel the ks_crt of alch_tunnel_create.  The error
- * terms are the caller's (alch_buf_gauss_dec, l, crt).  splitmix64 is a STATISTICAL generator, not a cryptographic one.
+ * terms are the caller's (alch_buf_gauss_dec, l, crt).  splitmix64 is a STATISTICAL generator, not a cryptographic one; a ring with a
+ * key (alch_ring_set_rng_key) draws a from a ChaCha20 keystream, and then also refuses positions that would reach 2^58.
  * n_v = 0: ALCH_OK, nothing queued.  ALCH_E_INVALID: null buffer; buffers of different rings; unknown gadget; a range or the key index
  * outside its buffer; the output range overlapping an input.  ALCH_E_NO_CRT: a ring without CRT basis. */
 int alch_ct_ks_hint(alch_buf *out, size_t out_first, int gadget, size_t n_v, const alch_buf *v_crt, size_t v_first,
@@ -672,6 +676,39 @@ int alch_ct_ks_hint(alch_buf *out, size_t out_first, int gadget, size_t n_v, con
 int alch_ct_ks_hint_part(alch_buf *out, size_t out_first, int gadget, size_t e_first, size_t e_count, const alch_buf *v_crt,
                          size_t v_first, const alch_buf *err_crt, size_t err_first, const alch_buf *sk_crt, size_t sk_index,
                          uint64_t seed, uint64_t ct0);
+
+/* ---- keyed streams for the samplers (added within 1.8; probe for the symbols) ------------------------------------------------------
+ * An opt-in 256-bit key per ring.  With a key set, the three samplers above draw their random words from ChaCha20 keystreams addressed
+ * by (key, seed, domain, position) instead of splitmix64 on a counter; with no key set nothing changes, bit for bit.  The key of the
+ * ring that is WRITTEN applies: dst of alch_buf_gauss_dec, out of alch_ct_encrypt, alch_ct_ks_hint and alch_ct_ks_hint_part.
+ * alch_buf_fill_uniform never looks at it.  Definition (alchemy_amd/csrc/chacha_stream.hpp):
+ *   block      ChaCha20, original layout, 20 rounds: state words 0-3 the constants 0x61707865 0x3320646e 0x79622d32 0x6b206574, words
+ *              4-11 the key as eight little-endian 32-bit words, words 12, 13 a 64-bit block counter (low, high), words 14, 15 a
+ *              64-bit nonce (low, high); output = working state + input state; u64[t] = word[2t] | word[2t+1] << 32, t < 8
+ *   address    nonce = the call's `seed` as given; position 0 <= x < 2^58 (a plain integer) of domain 0 <= d < 256 has block counter
+ *              (d << 56) | (x >> 2) and owns the pair (A, B) = (u64[2s], u64[2s+1]), s = x & 3
+ *   domain 1   alch_buf_gauss_dec: x = c = (elem0 + e) n + i; w0 = A, w1 = B -- deviate, scale, correlation and rounding as above
+ *   domain 2   alch_ct_encrypt: x = ((2 (ct0 + b) + 1) L + j) n + k; the c1 word is (B 2^64 + A) mod q_j
+ *   domain 3   alch_ct_ks_hint / _part: the same x with e for b; the a word is (B 2^64 + A) mod q_j
+ *   other domains are reserved.  One seed in two domains never shares keystream.
+ * A uniform word taken from 128 bits is within 2^-66 of uniform (q < 2^62).  elem0 / ct0 still only shift x: a batch cut anywhere,
+ * inside a block included, gives the words of one call.  A keystream must not wrap: a keyed call whose largest x would reach 2^58
+ * -- (elem0 + count) n > 2^58, 2 (ct0 + batch) L n > 2^58, computed without wrap-around -- returns ALCH_E_INVALID with nothing
+ * queued; unkeyed calls keep their arithmetic mod 2^64.
+ * CLAIMED: the words are a ChaCha20 keystream under the caller's key; uniform words are within 2^-66 of uniform.  THE CALLER'S DUTY: a
+ * (key, seed) pair is used for ONE batch per entry point, as any nonce is.  NOT CLAIMED: constant time (the table search and the
+ * reductions depend on the words); a better Gaussian than the staircase above; anything about the host path's mt19937_64. */
+#define ALCH_RNG_SPLITMIX 0
+#define ALCH_RNG_CHACHA20 1
+/* key: 32 bytes, copied into the ring under the device lock; NULL goes back to splitmix64.  The library keeps the key on the host only
+ * (zeroed on reset and in alch_ring_destroy) and passes it to kernels by value: no device memory is allocated for it.  Any ring,
+ * alch_ring_create_nocrt's included (the Gaussian writes into those). */
+int alch_ring_set_rng_key(alch_ring *ring, const void *key);
+/* ALCH_RNG_SPLITMIX or ALCH_RNG_CHACHA20; ALCH_E_INVALID: null ring. */
+int alch_ring_rng(const alch_ring *ring);
+/* Host only (no device needed): out[2i], out[2i + 1] = the pair (A, B) of position x0 + i, i < count, of (key, nonce, domain) -- the
+ * definition made callable.  key: 32 bytes.  ALCH_E_INVALID: null pointer; domain > 255; x0 + count > 2^58. */
+int alch_rng_words(const void *key, uint64_t nonce, unsigned domain, uint64_t x0, size_t count, uint64_t *out);
 
 /* ---- modSwitch building block (Eval.hs:130) ---------------------------------------
  * Rescale (a,b) -> b on Pow-basis elements: src lives in ring_src (L limbs), dst in ring_dst whose
