@@ -1,0 +1,71 @@
+"""Galois automorphisms sigma_j : zeta_m -> zeta_m^j on device-resident batches (include/alchemy_hip.h, "Galois automorphisms":
+alch_automorph_table, alch_buf_automorph, alch_automorph_create / _free, alch_ct_automorph).
+
+On the CRT basis sigma_j is a permutation of slots, crt(sigma_j a)[slot(u)] = crt(a)[slot(u j mod m)]; on a ciphertext it is that
+permutation of (c0, c1) followed by ONE linear key switch from sigma_j(s) back to s.  The hint of that key switch is an ordinary
+ksHint for the value sigma_j(s): `automorph_hint` composes it as `ks_hint` composes every other hint, so seeds, chunking and keyed
+streams (Ring.set_rng_key) apply unchanged."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from .capi import ALCH_GAD_TRIV, Buf, Ring, _check, _pu64, load_library
+from .hints import ks_hint
+
+
+def automorph_table(m: int, j: int) -> np.ndarray:
+    """Host only (no GPU needed): entry k is the SOURCE slot of destination slot k under sigma_j on the CRT basis of index m."""
+    lib, n = load_library(), C.c_size_t(0)
+    _check(lib.alch_automorph_table(m, j % (1 << 32), None, C.byref(n)))
+    out = np.zeros(n.value, dtype=np.uint32)
+    _check(lib.alch_automorph_table(m, j % (1 << 32), out.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(n)))
+    return out
+
+
+def buf_automorph(dst: Buf, src: Buf, j: int, count: int | None = None, dst_first: int = 0, src_first: int = 0):
+    """dst[dst_first + e] = sigma_j(src[src_first + e]), e < count, CRT-basis elements of one ring; the ranges share no byte."""
+    count = src.n_elems - src_first if count is None else count
+    _check(load_library().alch_buf_automorph(dst._h, dst_first, src._h, src_first, count, j % src.ring.m))
+
+
+def automorph_hint(ring: Ring, sk_crt: Buf, j: int, gadget: int = ALCH_GAD_TRIV, svar: float = 1.0, seed: int = 0) -> Buf:
+    """The 2 * D elements (b_t, a_t) with b_t + a_t s = g_t sigma_j(s) + e_t: ks_hint for the one value sigma_j(s)."""
+    v = ring.alloc(1)
+    buf_automorph(v, sk_crt, j, 1)
+    return ks_hint(ring, gadget, sk_crt, v, 1, svar, seed)
+
+
+class Automorph:
+    """alch_automorph: sigma_j on linear ciphertexts of `ring` at one key switch (the hint is copied: `ks_crt` may be reused)."""
+
+    def __init__(self, ring: Ring, j: int, ks_crt: Buf, gadget: int = ALCH_GAD_TRIV):
+        self.ring, self.j, self.gadget = ring, j % ring.m, gadget
+        h = C.c_void_p()
+        _check(ring._l.alch_automorph_create(ring._h, self.j, gadget, ks_crt._h, C.byref(h)))
+        self._h = h
+
+    def free(self):
+        if getattr(self, "_h", None):
+            if getattr(self.ring, "_h", None):                  # see Buf.free
+                self.ring._l.alch_automorph_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def ct_automorph(auto: Automorph, ct: Buf, batch: int, s_pre=None, out: Buf | None = None, flags: int = 0, meta=None):
+    """out[b] = keySwitch(sigma_j(ct[b])) for the `batch` linear ciphertexts (k = 0) of `ct`, CRT basis in and out; s_pre: toMSD's
+    per-limb scalar.  Returns the result buffer (a new one unless `out` is given), or (buffer, meta) when a CtMeta is passed: sigma_j
+    fixes Z_p and the call serves k = 0, so the record passes through unchanged (an encoding change made through s_pre is the
+    caller's to record, as for a tunnel)."""
+    if out is None:
+        out = auto.ring.alloc(max(1, 2 * batch))
+    sp = _pu64(s_pre) if s_pre is not None else None
+    _check(auto.ring._l.alch_ct_automorph(auto._h, ct._h, out._h, batch, sp, flags))
+    return out if meta is None else (out, meta)

@@ -53,6 +53,7 @@ SYMBOLS = [
     "alch_ct_ks_hint", "alch_ct_ks_hint_part",
     "alch_gadget_digits", "alch_decompose_baseb",
     "alch_ring_set_rng_key", "alch_ring_rng", "alch_rng_words",
+    "alch_automorph_table", "alch_buf_automorph", "alch_automorph_create", "alch_automorph_free", "alch_ct_automorph",
 ]
 
 
@@ -199,9 +200,16 @@ def load_library():
         "alch_ring_set_rng_key": [VP, C.c_char_p],
         "alch_ring_rng": [VP],
         "alch_rng_words": [C.c_char_p, C.c_uint64, C.c_uint, C.c_uint64, C.c_size_t, PU64],
+        "alch_automorph_table": [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)],
+        "alch_buf_automorph": [VP, C.c_size_t, VP, C.c_size_t, C.c_size_t, C.c_uint32],
+        "alch_automorph_create": [VP, C.c_uint32, C.c_int, VP, C.POINTER(VP)],
+        "alch_automorph_free": [VP],
+        "alch_ct_automorph": [VP, VP, VP, C.c_size_t, PU64, C.c_uint],
     }
     for name, args in sig.items():
-        fn = getattr(l, name)
+        fn = getattr(l, name, None)
+        if fn is None:                         # an older build named by ALCH_LIB_PATH (the header: "probe for the symbols"): calling it raises
+            continue
         fn.argtypes = args
         fn.restype = C.c_int
     _lib = l

@@ -115,6 +115,9 @@ struct alch_ring {
     void* gen_tables = nullptr;
     int* d_flag = nullptr;                     // divG failure flag
     std::deque<std::pair<u32, ExtTab>> ext;    // extension tables towards sub-rings of index .first (same moduli)
+    std::deque<std::pair<u32, u32*>> autotab;  // general engine: device slot tables of sigma_j, cached per j mod m (alch_buf_automorph)
+    void* ws_auto = nullptr;                   // alch_ct_automorph: the permuted ciphertexts of one chunk
+    size_t ws_auto_bytes = 0;
     // Free list of small device buffers: alch_buf_alloc / alch_buf_free of single ring elements are the allocation pattern of a
     // device-resident Tensor value (one buffer per `GT` value), and hipMalloc / hipFree cost 50-200 us and synchronise the device.
     // Reuse is stream-ordered: every consumer of a buffer on another ring's stream makes the owner's stream wait for it (ext_order,
@@ -1297,6 +1300,7 @@ __global__ void k_checksum(const W* data, size_t words, u64* sum, u64 w0) {
 #include "kernel_lift.hpp"
 #include "kernel_plain.hpp"
 #include "kernel_rlwe.hpp"
+#include "kernel_automorph.hpp"
 
 static inline unsigned ew_grid(size_t items) {
     size_t g = (items + 255) / 256;
@@ -1640,6 +1644,8 @@ extern "C" int alch_ring_destroy(alch_ring* r) try {
         if (e.second.slot_small) (void)hipFree(e.second.slot_small);
         if (e.second.fibres) (void)hipFree(e.second.fibres);
     }
+    for (auto& e : r->autotab) (void)hipFree(e.second);
+    if (r->ws_auto) (void)hipFree(r->ws_auto);
     if (r->tables_p) (void)hipFree(r->tables_p);
     if (r->ws_digits) (void)hipFree(r->ws_digits);
     if (r->ws_in) (void)hipFree(r->ws_in);
@@ -3950,6 +3956,158 @@ extern "C" int alch_ct_tunnel(const alch_tunnel* t, const alch_buf* in, alch_buf
     if (flags & ALCH_POW_OUT) if ((rc = buf_crt(out, 0, 2 * batch, true)) != ALCH_OK) return rc;
     if ((rc = ext_order(rs, rr, false)) != ALCH_OK) return rc;
     return rin != rr ? ext_order(rs, rin, false) : ALCH_OK;
+} catch (...) { return abi_catch(); }
+
+// ------------------------------------------------------------------------------------------------------
+// Galois automorphisms sigma_j on the CRT basis (include/alchemy_hip.h, "Galois automorphisms"; automorph_host.hpp)
+// ------------------------------------------------------------------------------------------------------
+extern "C" int alch_automorph_table(uint32_t m, uint32_t j, uint32_t* out, size_t* len) try {
+    if (!len) return fail(ALCH_E_INVALID, "null argument");
+    automorph::Plan P;
+    const int pc = automorph::plan(m, P);
+    if (pc == automorph::PLAN_INVALID) return fail(ALCH_E_INVALID, "cyclotomic index must be >= 1");
+    if (pc != automorph::PLAN_OK)
+        return fail(ALCH_E_UNSUPPORTED, "alch_automorph_table: index " + std::to_string(m) + " is served on neither engine (odd primes <= 13, phi(m) <= 65535; two-power m <= 2^17)");
+    if (automorph::gcd(j % m, m) != 1) return fail(ALCH_E_INVALID, "alch_automorph_table: j is not a unit mod m");
+    if (!out) { *len = P.n; return ALCH_OK; }
+    if (*len < P.n) return fail(ALCH_E_INVALID, "alch_automorph_table: capacity below phi(m)");
+    std::vector<uint32_t> t;
+    automorph::build_table(P, j, t);
+    memcpy(out, t.data(), t.size() * sizeof(uint32_t));
+    *len = P.n;
+    return ALCH_OK;
+} catch (...) { return abi_catch(); }
+
+// General engine: the device table of sigma_j (j reduced mod m, a unit), cached in the ring.  At most AUTOTAB_MAX tables stay; the
+// oldest leaves after the stream has drained (a queued gather may still read it).
+constexpr size_t AUTOTAB_MAX = 64;
+static int automorph_dev_table(alch_ring* r, u32 j, const u32** out) {
+    for (auto& e : r->autotab) if (e.first == j) { *out = e.second; return ALCH_OK; }
+    automorph::Plan P;
+    std::vector<uint32_t> t;
+    if (automorph::plan(r->m, P) != automorph::PLAN_OK || P.n != r->n || !automorph::build_table(P, j, t))
+        return fail(ALCH_E_INTERNAL, "automorphism table: the ring's index has no plan");
+    if (r->autotab.size() >= AUTOTAB_MAX) {
+        HIP_TRY(hipStreamSynchronize(r->stream));
+        (void)hipFree(r->autotab.front().second);
+        r->autotab.pop_front();
+    }
+    u32* d = nullptr;
+    if (hipMalloc((void**)&d, t.size() * sizeof(u32)) != hipSuccess) return fail(ALCH_E_NOMEM, "hipMalloc(automorphism table) failed");
+    if (hipMemcpy(d, t.data(), t.size() * sizeof(u32), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        return fail(ALCH_E_HIP, "automorphism table upload failed");
+    }
+    r->autotab.emplace_back(j, d);
+    *out = d;
+    return ALCH_OK;
+}
+
+// dst[e] = sigma_j(src[e]), e < count, CRT basis; dst and src share no byte (the callers check).  tab: general engine only.
+template <typename W>
+static int launch_automorph(alch_ring* r, void* dst, const void* src, size_t count, u32 j, const u32* tab) {
+    constexpr int VL = Vec4<W>::LANES;
+    const size_t words = count * elem_words(r);
+    if (!r->gen)                                   // n >= 16: a multiple of the vector width
+        hipLaunchKernelGGL((k_automorph_pow2<W, VL>), dim3(ew_grid(words / VL)), dim3(256), 0, r->stream, dev_ring<W>(r), (W*)dst, (const W*)src, words, j, r->logn);
+    else if (r->n % VL == 0)
+        hipLaunchKernelGGL((k_automorph_tab<W, VL>), dim3(ew_grid(words / VL)), dim3(256), 0, r->stream, dev_ring<W>(r), (W*)dst, (const W*)src, words, tab);
+    else
+        hipLaunchKernelGGL((k_automorph_tab<W, 1>), dim3(ew_grid(words)), dim3(256), 0, r->stream, dev_ring<W>(r), (W*)dst, (const W*)src, words, tab);
+    HIP_TRY(hipGetLastError());
+    return ALCH_OK;
+}
+
+extern "C" int alch_buf_automorph(alch_buf* dst, size_t dst_first, const alch_buf* src, size_t src_first, size_t count, uint32_t j) try {
+    if (!dst || !src) return fail(ALCH_E_INVALID, "null buffer");
+    if (dst->ring != src->ring) return fail(ALCH_E_INVALID, "buffers belong to different rings");
+    if (!range_ok(dst_first, count, dst->n_elems) || !range_ok(src_first, count, src->n_elems)) return fail(ALCH_E_INVALID, "element range out of bounds");
+    alch_ring* r = dst->ring;
+    if (!r->has_crt) return fail(ALCH_E_NO_CRT, "this ring has no CRT basis (created with alch_ring_create_nocrt)");
+    j %= r->m;
+    if (automorph::gcd(j, r->m) != 1) return fail(ALCH_E_INVALID, "alch_buf_automorph: j is not a unit mod m");
+    if (count == 0) return ALCH_OK;
+    BIND(r);
+    char* d = reinterpret_cast<char*>(dst->dptr) + dst_first * elem_bytes(r);
+    const char* f = reinterpret_cast<const char*>(src->dptr) + src_first * elem_bytes(r);
+    if (bytes_overlap(d, count * elem_bytes(r), f, count * elem_bytes(r)))
+        return fail(ALCH_E_INVALID, "alch_buf_automorph: the written range overlaps the read range (a gather cannot run in place)");
+    const u32* tab = nullptr;
+    int rc;
+    if (r->gen && (rc = automorph_dev_table(r, j, &tab)) != ALCH_OK) return rc;
+    return ALCH_BY_WORD(r, launch_automorph, r, d, f, count, j, tab);
+} catch (...) { return abi_catch(); }
+
+// sigma_j on linear ciphertexts at one key switch: the gather into the ring's scratch, then the ring-to-itself tunnel stage with
+// lin = crt(1) and d_rel = 1 -- out = (s_pre sigma_j(c0), 0) + switch(hint, s_pre sigma_j(c1)) -- on the permuted chunk.  The
+// tunnel kernels are the ones alch_ct_tunnel runs, so the words are those of alch_buf_automorph followed by alch_ct_tunnel.
+struct alch_automorph {
+    alch_ring* ring;
+    u32 j;                                     // reduced mod m
+    alch_tunnel* tun;                          // ring -> ring, lin = crt(1), the caller's hint (owned)
+};
+
+extern "C" int alch_automorph_create(alch_ring* ring, uint32_t j, int gadget, const alch_buf* ks_crt, void** out) try {
+    if (!ring || !ks_crt || !out) return fail(ALCH_E_INVALID, "null argument");
+    *out = nullptr;
+    if (gadget_width(gadget) < 0) return fail(ALCH_E_INVALID, "alch_automorph_create: unknown gadget");
+    if (ks_crt->ring != ring) return fail(ALCH_E_INVALID, "alch_automorph_create: the hint lives in the ring");
+    if (!ring->has_crt) return fail(ALCH_E_NO_CRT, "this ring has no CRT basis (created with alch_ring_create_nocrt)");
+    j %= ring->m;
+    if (automorph::gcd(j, ring->m) != 1) return fail(ALCH_E_INVALID, "alch_automorph_create: j is not a unit mod m");
+    if (ks_crt->n_elems < 2 * (size_t)gadget_digits(ring, gadget)) return fail(ALCH_E_INVALID, "alch_automorph_create: need 2 * (gadget digits) hint elements");
+    BIND(ring);
+    int rc;
+    const u32* tab = nullptr;
+    if (ring->gen && (rc = automorph_dev_table(ring, j, &tab)) != ALCH_OK) return rc;
+    alch_buf* one = nullptr;                   // crt(1): the constant 1 in every slot of every limb
+    if ((rc = alch_buf_alloc(ring, 1, &one)) != ALCH_OK) return rc;
+    std::vector<int64_t> ones(elem_words(ring), 1);
+    alch_tunnel* t = nullptr;
+    if ((rc = alch_buf_upload(one, 0, 1, ones.data())) == ALCH_OK) rc = alch_tunnel_create(ring, ring, gadget, one, ks_crt, &t);
+    const std::string msg = g_err;             // alch_tunnel_create has drained the stream: `one` and `ones` are no longer read
+    alch_buf_free(one);
+    if (rc != ALCH_OK) return fail(rc, msg);
+    *out = new alch_automorph{ring, j, t};
+    return ALCH_OK;
+} catch (...) { return abi_catch(); }
+
+extern "C" int alch_automorph_free(void* handle) try {
+    alch_automorph* a = reinterpret_cast<alch_automorph*>(handle);
+    if (!a) return ALCH_OK;
+    alch_tunnel_free(a->tun);
+    delete a;
+    return ALCH_OK;
+} catch (...) { return abi_catch(); }
+
+extern "C" int alch_ct_automorph(const void* handle, const alch_buf* in, alch_buf* out, size_t batch, const uint64_t* s_pre, unsigned flags) try {
+    const alch_automorph* a = reinterpret_cast<const alch_automorph*>(handle);
+    if (!a || !in || !out) return fail(ALCH_E_INVALID, "null argument");
+    alch_ring* r = a->ring;
+    if (in->ring != r || out->ring != r) return fail(ALCH_E_INVALID, "alch_ct_automorph: input and output buffers belong to the automorphism's ring");
+    if (flags & ~(unsigned)(ALCH_POW_IN | ALCH_POW_OUT)) return fail(ALCH_E_INVALID, "unknown flag");
+    if (flags) return fail(ALCH_E_UNSUPPORTED, "alch_ct_automorph: CRT basis in and out only (on the powerful basis sigma_j is not a permutation: transform first)");
+    if (batch == 0) return ALCH_OK;
+    if (!pairs_ok(batch, in->n_elems) || !pairs_ok(batch, out->n_elems)) return fail(ALCH_E_INVALID, "buffers must hold 2*batch ring elements");
+    const size_t eb = elem_bytes(r);
+    if (bytes_overlap(out->dptr, 2 * batch * eb, in->dptr, 2 * batch * eb)) return fail(ALCH_E_INVALID, "alch_ct_automorph: out must not alias the input");
+    BIND(r);
+    int rc;
+    const u32* tab = nullptr;
+    if (r->gen && (rc = automorph_dev_table(r, a->j, &tab)) != ALCH_OK) return rc;
+    size_t chunk = std::max<size_t>(1, (r->scratch_mib << 20) / (2 * eb));
+    chunk = std::min(chunk, batch);
+    if ((rc = ensure_ws(&r->ws_auto, &r->ws_auto_bytes, chunk * 2 * eb)) != ALCH_OK) return rc;
+    for (size_t done = 0; done < batch; done += chunk) {
+        const size_t now = std::min(chunk, batch - done);
+        const char* src = reinterpret_cast<const char*>(in->dptr) + done * 2 * eb;
+        char* dst = reinterpret_cast<char*>(out->dptr) + done * 2 * eb;
+        if ((rc = ALCH_BY_WORD(r, launch_automorph, r, r->ws_auto, src, 2 * now, a->j, tab)) != ALCH_OK) return rc;
+        if (a->tun->pow2) rc = ALCH_BY_WORD(r, do_tunnel_pow2, a->tun, r, r->ws_auto, dst, now, s_pre, 0u);
+        else rc = ALCH_BY_WORD(r, do_tunnel, a->tun, r, r->ws_auto, dst, now, s_pre, 0u);
+        if (rc != ALCH_OK) return rc;
+    }
+    return ALCH_OK;
 } catch (...) { return abi_catch(); }
 
 // ------------------------------------------------------------------------------------------------------

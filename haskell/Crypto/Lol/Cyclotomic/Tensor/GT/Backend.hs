@@ -166,3 +166,10 @@ foreign import ccall safe   "alch_ct_ks_hint_part"     c_ctKsHintPart    :: Ptr 
 foreign import ccall safe   "alch_ring_set_rng_key"    c_ringSetRngKey   :: Ptr AlchRing -> Ptr () -> IO CInt
 foreign import ccall unsafe "alch_ring_rng"            c_ringRng         :: Ptr AlchRing -> IO CInt
 foreign import ccall safe   "alch_rng_words"           c_rngWords        :: Ptr () -> Word64 -> CUInt -> Word64 -> CSize -> Ptr Word64 -> IO CInt
+-- Galois automorphisms sigma_j (include/alchemy_hip.h, "Galois automorphisms"): the slot table is host-only and takes no lock (a pure
+-- accessor, like alch_ext_table); the handle of the ciphertext operation is untyped, like alch_pt_linear_create's
+foreign import ccall unsafe "alch_automorph_table"     c_automorphTable  :: Word32 -> Word32 -> Ptr Word32 -> Ptr CSize -> IO CInt
+foreign import ccall safe   "alch_buf_automorph"       c_bufAutomorph    :: Ptr AlchBuf -> CSize -> Ptr AlchBuf -> CSize -> CSize -> Word32 -> IO CInt
+foreign import ccall safe   "alch_automorph_create"    c_automorphCreate :: Ptr AlchRing -> Word32 -> CInt -> Ptr AlchBuf -> Ptr (Ptr ()) -> IO CInt
+foreign import ccall safe   "alch_automorph_free"      c_automorphFree   :: Ptr () -> IO CInt
+foreign import ccall safe   "alch_ct_automorph"        c_ctAutomorph     :: Ptr () -> Ptr AlchBuf -> Ptr AlchBuf -> CSize -> Ptr Word64 -> CUInt -> IO CInt

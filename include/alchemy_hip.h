@@ -253,8 +253,8 @@ int alch_buf_view(const alch_buf *parent, size_t first, size_t count, alch_buf *
  *   alch_hint_from_buf, alch_tunnel_create, alch_pt_linear_create   copy their sources: the sources may be overwritten afterwards
  * Entry points between two rings whose limb counts differ (alch_ct_mod_switch(_deg), alch_buf_rescale_drop0 / _add0) cannot be
  * given overlapping ranges: a view keeps its parent's ring.  Those that accept one ring on both sides (alch_buf_embed / _twace /
- * _coeffs with equal indices, alch_ct_tunnel from a ring to itself, alch_ct_mul_full with operands and result on one ring)
- * follow the rule without exception. */
+ * _coeffs with equal indices, alch_ct_tunnel from a ring to itself, alch_ct_mul_full with operands and result on one ring,
+ * alch_buf_automorph, alch_ct_automorph) follow the rule without exception. */
 int alch_buf_elems(const alch_buf *buf, size_t *n_elems);
 /* Device address and size of the buffer (limb-major words, see above) for zero-copy hand-off to other device
  * code on the same GPU -- RCCL collectives that gather result batches, a caller's own kernels.
@@ -464,6 +464,49 @@ int alch_tunnel_create(alch_ring *ring_r, alch_ring *ring_s, int gadget, const a
                        alch_tunnel **out);
 int alch_tunnel_free(alch_tunnel *t);
 int alch_ct_tunnel(const alch_tunnel *t, const alch_buf *in, alch_buf *out, size_t batch, const uint64_t *s_pre, unsigned flags);
+
+/* ---- Galois automorphisms (added within 1.8; probe for the symbols) ---------------------------------------------------------------
+ * sigma_j : zeta_m -> zeta_m^j for gcd(j, m) = 1, the third primitive of ciphertext arithmetic next to (+) and (*): on a plaintext a
+ * rotation / permutation of its CRT slots, conjugation for j = -1.  The reference's evaluator has no such operation (its rotations are
+ * ring tunnels); a ring-to-itself alch_ct_tunnel computes sigma_j only where it is E'-linear for a subring of index e' with j = 1 mod e',
+ * at d_rel = phi(m') / phi(e') key switches.  These entry points cost ONE key switch for every unit j.
+ * DEFINITION.  sigma_j fixes Z_q, so on the CRT basis it moves slots and nothing else.  By the slot rule at the top of this file slot(u)
+ * holds a(omega_m^u), hence
+ *       crt(sigma_j a)[slot(u)] = crt(a)[slot(u j mod m)]
+ *   two-power index: slot k holds the unit 2 brev(k) + 1;  general index: slot (s_1..s_k) holds u = i0 + p i1 on every prime-power axis.
+ * The permutation is the same for every limb and factorises over the prime-power axes.  j is reduced mod m everywhere.
+ * ON CIPHERTEXTS.  (sigma_j c0, sigma_j c1) decrypts under sigma_j(s); one LINEAR key switch takes it back under s:
+ *       out = (s_pre sigma_j c0, 0) + sum_t D_t (b_t, a_t),   D_t = the transformed gadget digits of s_pre sigma_j c1,
+ * with a hint b_t + a_t s = g_t sigma_j(s) + e_t -- what alch_ct_ks_hint writes for n_v = 1 and v = sigma_j(s).  That key switch is
+ * exactly the tunnel from the ring to itself with lin_crt = crt(1) (d_rel = 1). */
+/* Host-only (no GPU needed), like alch_ext_table: out[k] = the SOURCE slot of destination slot k, k < phi(m).  *len in = capacity of
+ * out (entries), out = phi(m); out == NULL queries the length.  ALCH_E_INVALID: null len, capacity too small, gcd(j, m) != 1, m = 0.
+ * ALCH_E_UNSUPPORTED: an index neither engine serves (alch_ring_create's rule without its word-size test: an odd prime above 13,
+ * phi(m) > 65535, a two-power m > 2^17). */
+int alch_automorph_table(uint32_t m, uint32_t j, uint32_t *out, size_t *len);
+/* dst[dst_first + e] = sigma_j(src[src_first + e]), e < count: both buffers on one ring with a CRT basis, elements in the CRT basis.
+ * Queued on the ring's stream; the source is left as it was.  A gather cannot run in place: the written range must share no byte with
+ * the read range ("Overlapping ranges" above; adjacent views are fine), else ALCH_E_INVALID naming this function, nothing launched.
+ * Two-power m >= 32 (the split sizes included): the source slot is a closed form per lane, no table; any other index: a phi(m)-entry
+ * device table cached in the ring per j.  count = 0: ALCH_OK, nothing queued.  Statuses, in this order: ALCH_E_INVALID (null buffer;
+ * different rings; a range outside its buffer), ALCH_E_NO_CRT (a ring from alch_ring_create_nocrt), ALCH_E_INVALID (j not a unit;
+ * overlap), device errors last. */
+int alch_buf_automorph(alch_buf *dst, size_t dst_first, const alch_buf *src, size_t src_first, size_t count, uint32_t j);
+/* The ciphertext operation.  The handle is the library's `alch_automorph`, declared as an untyped `void *` for the reason given at
+ * alch_pt_linear_create (the FFI check's type table has no entry for a new handle type); alchemy_amd.Automorph wraps it.
+ *   gadget  any gadget code, ALCH_GAD_BASEPOW2(w) included; D = its digit count on `ring` (alch_gadget_digits)
+ *   ks_crt  2 * D elements of `ring`, CRT basis, the layout of alch_hint_from_buf: b_0, a_0, b_1, a_1, ... with
+ *           b_t + a_t s = g_t sigma_j(s) + e_t.  Copied (Montgomery form) at create time: the source may be overwritten afterwards.
+ * alch_ct_automorph serves linear ciphertexts with k = 0 (elements (2b, 2b+1)), `in` and `out` on `ring`, CRT basis in and out;
+ * s_pre = toMSD's per-limb scalar (NULL = 1).  The result is WORD FOR WORD what alch_buf_automorph on the batch followed by
+ * alch_ct_tunnel from the ring to itself (lin_crt = crt(1), the same ks_crt) returns: the gather goes into a scratch area of the ring,
+ * the tunnel's key-switch stage runs on it; both walk the batch in chunks of at most "scratch_mib".  The input is not modified; `out`
+ * must not overlap `in`.  ALCH_POW_IN / ALCH_POW_OUT: ALCH_E_UNSUPPORTED (on the powerful basis sigma_j is not a permutation; callers
+ * transform).  k > 0: absorbGFactors first, exactly as documented for alch_ct_tunnel.  batch = 0: ALCH_OK, nothing queued.
+ * Free the handle with alch_automorph_free when no call is using it (it does not take the device lock, like the other *_free). */
+int alch_automorph_create(alch_ring *ring, uint32_t j, int gadget, const alch_buf *ks_crt, void **out);
+int alch_automorph_free(void *a);
+int alch_ct_automorph(const void *a, const alch_buf *in, alch_buf *out, size_t batch, const uint64_t *s_pre, unsigned flags);
 
 /* ---- SymmSHE modSwitch on batches of linear ciphertexts (Eval.hs:130; the two modSwitch_ of PT2CT.hs:177 and :224-229) ----
  * The rings come from the handles; the smaller ring's moduli are the LAST limbs of the bigger ring's (Noise.hs:82-89).  The
