@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -22,6 +23,7 @@
 #include "ring_host.hpp"
 #include "gen_host.hpp"
 #include "plain_host.hpp"
+#include "scratch_plan.hpp"
 #include "chacha_stream.hpp"
 
 using namespace alch;
@@ -56,6 +58,14 @@ struct StreamOwner {
     StreamOwner& operator=(const StreamOwner&) = delete;
 };
 
+// One device arena of a ring: grown on demand (freed and allocated anew, the old words are not kept), never shrunk.
+struct Scratch {
+    void* p = nullptr;
+    size_t bytes = 0;
+    int reserve(size_t need);
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+};
+
 struct alch_ring {
     u32 m = 0, n = 0;
     int logn = 0, L = 0, word = 0;            // word = 4 or 8 bytes per residue on the device
@@ -72,25 +82,18 @@ struct alch_ring {
     void* tables_p = nullptr;                  // Plantard forward constants (32-bit rings) / Shoup pairs (64-bit rings)
     DevRing<u32> d32;
     DevRing<u64> d64;
-    void* ws_digits = nullptr;                 // digit scratch, two halves of [chunk][L][n] signed words
-    size_t ws_digits_bytes = 0;
+    Scratch ws_digits;                         // digit scratch, two halves of [chunk][L][n] signed words
     hipStream_t aux = nullptr;                 // second pipeline of ct_mul_relin (odd chunks)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    void* ws_in = nullptr;                     // crt scratch for ALCH_POW_IN (2 * 2*batch elements)
-    size_t ws_in_bytes = 0;
-    void* ws_host = nullptr;                   // staging for the host-buffer Tensor methods
-    size_t ws_host_bytes = 0;
+    Scratch ws_in;                             // crt scratch for ALCH_POW_IN (2 * 2*batch elements)
+    Scratch ws_host;                           // staging for the host-buffer Tensor methods
     u64* ws_sum = nullptr;                     // checksum accumulator
     size_t chunk = 1024;                       // ciphertexts per (tensor_intt, ks_accum) launch pair
-    void* ws_full = nullptr;                   // ct_mul_full scratch: per pipeline digits + key-switched chunk + stash
-    size_t ws_full_bytes = 0;
+    Scratch ws_full;                           // ct_mul_full scratch: per pipeline digits + key-switched chunk + stash
     hipEvent_t ev_x = nullptr;                 // cross-ring ordering (ext_order)
-    void* ws_lift = nullptr;                   // decrypt / error-rate scratch: c(s) of one chunk (+ its crt'd inputs with ALCH_POW_IN)
-    size_t ws_lift_bytes = 0;
-    void* ws_maxd = nullptr;                   // digit vectors of max |lift|, 8 L bytes per element
-    size_t ws_maxd_bytes = 0;
-    void* ws_gauss = nullptr;                  // alch_buf_gauss_dec on an index with odd primes: the doubles of one chunk of elements
-    size_t ws_gauss_bytes = 0;
+    Scratch ws_lift;                           // decrypt / error-rate scratch: c(s) of one chunk (+ its crt'd inputs with ALCH_POW_IN)
+    Scratch ws_maxd;                           // digit vectors of max |lift|, 8 L bytes per element
+    Scratch ws_gauss;                          // alch_buf_gauss_dec on an index with odd primes: the doubles of one chunk of elements
     bool rng_keyed = false;                    // alch_ring_set_rng_key: the samplers that write into this ring draw from ChaCha20 keystreams
     chacha::Key rng_key = {{0}};               // host copy only: it reaches the kernels by value, zeroed on reset and on destroy
     int device = 0;                            // HIP device the ring's streams, tables and buffers live on
@@ -116,8 +119,7 @@ struct alch_ring {
     int* d_flag = nullptr;                     // divG failure flag
     std::deque<std::pair<u32, ExtTab>> ext;    // extension tables towards sub-rings of index .first (same moduli)
     std::deque<std::pair<u32, u32*>> autotab;  // general engine: device slot tables of sigma_j, cached per j mod m (alch_buf_automorph)
-    void* ws_auto = nullptr;                   // alch_ct_automorph: the permuted ciphertexts of one chunk
-    size_t ws_auto_bytes = 0;
+    Scratch ws_auto;                           // alch_ct_automorph: the permuted ciphertexts of one chunk
     // Free list of small device buffers: alch_buf_alloc / alch_buf_free of single ring elements are the allocation pattern of a
     // device-resident Tensor value (one buffer per `GT` value), and hipMalloc / hipFree cost 50-200 us and synchronise the device.
     // Reuse is stream-ordered: every consumer of a buffer on another ring's stream makes the owner's stream wait for it (ext_order,
@@ -1645,16 +1647,9 @@ extern "C" int alch_ring_destroy(alch_ring* r) try {
         if (e.second.fibres) (void)hipFree(e.second.fibres);
     }
     for (auto& e : r->autotab) (void)hipFree(e.second);
-    if (r->ws_auto) (void)hipFree(r->ws_auto);
     if (r->tables_p) (void)hipFree(r->tables_p);
-    if (r->ws_digits) (void)hipFree(r->ws_digits);
-    if (r->ws_in) (void)hipFree(r->ws_in);
-    if (r->ws_full) (void)hipFree(r->ws_full);
-    if (r->ws_lift) (void)hipFree(r->ws_lift);
-    if (r->ws_maxd) (void)hipFree(r->ws_maxd);
-    if (r->ws_gauss) (void)hipFree(r->ws_gauss);
+    for (Scratch* w : {&r->ws_auto, &r->ws_digits, &r->ws_in, &r->ws_full, &r->ws_lift, &r->ws_maxd, &r->ws_gauss, &r->ws_host}) w->release();
     if (r->ev_x) (void)hipEventDestroy(r->ev_x);
-    if (r->ws_host) (void)hipFree(r->ws_host);
     if (r->ws_sum) (void)hipFree(r->ws_sum);
     if (r->ev0) (void)hipEventDestroy(r->ev0);
     if (r->ev1) (void)hipEventDestroy(r->ev1);
@@ -1813,11 +1808,11 @@ static inline bool split_ring(const alch_ring* r) { return r->logn > (r->word ==
 static inline size_t elem_words(const alch_ring* r) { return (size_t)r->L * r->n; }
 static inline size_t elem_bytes(const alch_ring* r) { return elem_words(r) * (size_t)r->word; }
 
-static int ensure_ws(void** p, size_t* have, size_t need) {
-    if (*have >= need) return ALCH_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *have = 0; }
-    if (hipMalloc(p, need) != hipSuccess) return fail(ALCH_E_NOMEM, "hipMalloc(" + std::to_string(need) + ") failed");
-    *have = need;
+int Scratch::reserve(size_t need) {
+    if (bytes >= need) return ALCH_OK;
+    release();
+    if (hipMalloc(&p, need) != hipSuccess) return fail(ALCH_E_NOMEM, "hipMalloc(" + std::to_string(need) + ") failed");
+    bytes = need;
     return ALCH_OK;
 }
 
@@ -1893,6 +1888,20 @@ static int do_crt(alch_ring* r, void* data, size_t first_elem, size_t count, boo
         done += now;
     }
     return ALCH_OK;
+}
+
+// Transformed copies of `srcs` (count_each elements each) in consecutive regions of dst.  The split transforms (n = 2^16 / 64-bit 2^15)
+// work in place only: one copy per source, then ONE transform over all of them; every other ring transforms out of place from each source.
+template <typename W>
+static int crt_into(alch_ring* r, void* dst, std::initializer_list<const void*> srcs, size_t count_each, bool inverse, const alch_ring* on = nullptr) {
+    const size_t bytes = count_each * elem_bytes(r);
+    char* d = reinterpret_cast<char*>(dst);
+    for (const void* src : srcs) {
+        if (split_ring(r)) HIP_TRY(hipMemcpyAsync(d, src, bytes, hipMemcpyDeviceToDevice, (on ? on : r)->stream));
+        else if (int rc = do_crt<W>(r, d, 0, count_each, inverse, src, on)) return rc;
+        d += bytes;
+    }
+    return split_ring(r) ? do_crt<W>(r, dst, 0, srcs.size() * count_each, inverse, nullptr, on) : ALCH_OK;
 }
 
 static int buf_crt(alch_buf* b, size_t first, size_t count, bool inverse) {
@@ -1998,9 +2007,9 @@ extern "C" int alch_ring_device(const alch_ring* r, int* device, void** hip_stre
 template <typename W>
 static int do_transfer(alch_ring* r, void* dev, size_t count, int64_t* host, bool to_device) {
     const size_t bytes = count * elem_words(r) * sizeof(int64_t);
-    int rc = ensure_ws(&r->ws_host, &r->ws_host_bytes, bytes);
+    int rc = r->ws_host.reserve(bytes);
     if (rc != ALCH_OK) return rc;
-    int64_t* stage = reinterpret_cast<int64_t*>(r->ws_host);
+    int64_t* stage = reinterpret_cast<int64_t*>(r->ws_host.p);
     const size_t total = count * elem_words(r);
     if (bytes <= PIN_MAX) {
         // small transfer (the per-Tensor-call path moves one ring element at a time): through a pinned slot
@@ -2593,11 +2602,8 @@ extern "C" int alch_buf_tensor_op(alch_buf* dst, size_t dst_first, const alch_bu
     int rc;
     if (op == ALCH_T_CRT || op == ALCH_T_CRTINV) {
         const bool inv = op == ALCH_T_CRTINV;
-        if (in_place || split_ring(r)) {                       // the split transforms (n = 2^16 / 64-bit 2^15) work in place only
-            if ((rc = copy_first()) != ALCH_OK) return rc;
-            return ALCH_BY_WORD(r, do_crt, r, d, 0, count, inv);
-        }
-        return ALCH_BY_WORD(r, do_crt, r, d, 0, count, inv, f);
+        if (in_place) return ALCH_BY_WORD(r, do_crt, r, d, 0, count, inv);
+        return ALCH_BY_WORD(r, crt_into, r, d, {f}, count, inv);
     }
     const bool trivial = !r->gen || r->gh.rad == 1;                   // two-power index: g = 1, L = identity
     if (trivial) return copy_first();
@@ -2777,8 +2783,7 @@ struct KsStage {
     size_t elems;               // scratch per ciphertext, in ring elements: c2 in both bases (unless it arrives ready) + digits (unless no_digits)
     Scal<W> sr2;                // the tensor product's scalar (times R^2)
     GTab<W> gt;
-    char* scratch;              // c2 | c2crt | dig, each for `chunk` ciphertexts (a ready c2: dig only)
-    size_t chunk;
+    W *c2, *c2crt, *dig;        // the stage's scratch, each for one chunk of ciphertexts: ks_stage_carve
 };
 
 template <typename W>
@@ -2796,24 +2801,29 @@ static KsStage<W> ks_stage_plan(alch_ring* r, const alch_hint* hint, int dup, bo
     if (!have_c2) s.gt = g_table<W>(r);
     return s;
 }
+// The stage's regions, next in the caller's arena: c2 | c2crt | dig (a ready c2 that is not the stage's own, BaseBGad 2 only: dig alone).
+template <typename W>
+static void ks_stage_carve(KsStage<W>& s, Carve& cv, size_t eb) {
+    const size_t c2_b = (s.have_c2 && !s.c2_both) ? 0 : eb;
+    s.c2 = reinterpret_cast<W*>(cv.take(c2_b));
+    s.c2crt = reinterpret_cast<W*>(cv.take(c2_b));                // CRT-basis copy of c2 (diagonal digits, split rings)
+    s.dig = reinterpret_cast<W*>(cv.take(s.no_digits ? 0 : s.D * eb));
+}
 
-// The stage for `now` <= s.chunk ciphertexts: out [now][2][L][n] = (c0, c1) of a * b + switch(hint, c2).  a, b: the operands on the last
+// The stage for `now` ciphertexts, at most the chunk it was carved for: out [now][2][L][n] = (c0, c1) of a * b + switch(hint, c2).  a, b: the operands on the last
 // L - s.dup limbs of r; or, for s.have_c2, c2pow: `now` elements of r, and out already holds (c0, c1).
 template <typename W>
 static int ks_stage(alch_ring* r, const KsStage<W>& s, const W* a, const W* b, const W* c2pow, W* out, size_t now) {
-    const size_t eb = elem_bytes(r);
     const int L = r->L, Ls = L - s.dup;
     const W* hint = reinterpret_cast<const W*>(s.hint->dptr);
-    char* c2crt = s.scratch + s.chunk * eb;                       // CRT-basis copy of c2 (diagonal digits, split rings)
-    W* dig = reinterpret_cast<W*>(s.have_c2 && !s.c2_both ? s.scratch : c2crt + s.chunk * eb);
-    W* diag = s.fused_digits ? reinterpret_cast<W*>(c2crt) : nullptr;   // have_c2 without c2_both: BaseBGad 2 only (no diagonal)
+    W *dig = s.dig, *diag = s.fused_digits ? s.c2crt : nullptr;
     NttCall<W> nc{};
     nc.ring = &dev_ring<W>(r); nc.stream = r->stream; nc.balanced = r->balanced;
     GenCall<W> gc{};
     gc.ring = &dev_ring<W>(r); gc.gen = &gen_dev<W>(r); gc.stream = r->stream; gc.balanced = r->balanced;
     int rc;
     if (!s.have_c2) {
-        W* c2 = reinterpret_cast<W*>(s.scratch);
+        W* c2 = s.c2;
         if constexpr (sizeof(W) == 4) {
             if (s.gen_fused) {                                    // two fused launches: tensor + crtInv, digit transforms + hint products
                 GenKsArgs<u32> A{};
@@ -2887,14 +2897,16 @@ static int do_mul_relin_unfused(alch_ring* r, const alch_hint* hint, const void*
                                 const uint64_t* s_pre, const void* c2pow = nullptr) {
     KsStage<W> s = ks_stage_plan<W>(r, hint, 0, c2pow != nullptr);
     const size_t per_ct = s.elems * elem_bytes(r);
-    s.chunk = std::min(batch, std::max<size_t>(1, (r->scratch_mib << 20) / per_ct));
-    int rc = ensure_ws(&r->ws_digits, &r->ws_digits_bytes, s.chunk * per_ct);
+    const size_t chunk = scratch_chunk(r->scratch_mib << 20, batch, per_ct);
+    int rc = r->ws_digits.reserve(chunk * per_ct);
     if (rc != ALCH_OK) return rc;
-    s.scratch = reinterpret_cast<char*>(r->ws_digits);
+    Carve cv(r->ws_digits.p, chunk);
+    ks_stage_carve(s, cv, elem_bytes(r));
+    if (!cv.matches(per_ct)) return fail(ALCH_E_INTERNAL, "do_mul_relin_unfused: the scratch carve differs from the bytes reserved per ciphertext");
     if (!c2pow) scal_to_mont<W>(r, s_pre, 2, s.sr2);
     const size_t ew = elem_words(r);
-    for (size_t done = 0; done < batch; done += s.chunk) {
-        const size_t now = std::min(s.chunk, batch - done);
+    for (size_t done = 0; done < batch; done += chunk) {
+        const size_t now = std::min(chunk, batch - done);
         const W* pa = c2pow ? nullptr : reinterpret_cast<const W*>(a) + done * 2 * ew;
         const W* pb = c2pow ? nullptr : reinterpret_cast<const W*>(b) + done * 2 * ew;
         const W* pc = c2pow ? reinterpret_cast<const W*>(c2pow) + done * ew : nullptr;
@@ -2912,12 +2924,10 @@ static int do_mul_relin(alch_ring* r, const alch_hint* hint, const void* a, cons
     // small enough for them to stay in the 256 MiB Infinity Cache; to keep the GPU full across the kernel
     // boundaries of such small launches, even and odd chunks run as two independent pipelines on two streams
     // (each with its own digit scratch), so one pipeline's tail overlaps the other's head.
-    // the key-switch kernel addresses each array with 32-bit byte offsets: a chunk's ciphertexts stay below 4 GiB
-    const size_t cap = std::max<size_t>(8, (((size_t)1 << 32) - 1) / (2 * elem_bytes(r)) / 8 * 8);
-    const size_t chunk = std::min(std::min(r->chunk, cap), (batch + 7) / 8 * 8);
+    const size_t chunk = fused_chunk(r->chunk, 2 * elem_bytes(r), batch);        // 32-bit byte offsets per array, groups of 8
     const size_t dig_bytes = chunk * elem_words(r) * sizeof(SW);
     const int ns = r->one_stream ? 1 : r->nstreams;
-    int rc = ensure_ws(&r->ws_digits, &r->ws_digits_bytes, (size_t)std::max(2, ns) * dig_bytes);
+    int rc = r->ws_digits.reserve((size_t)std::max(2, ns) * dig_bytes);
     if (rc != ALCH_OK) return rc;
     for (int e = 0; e + 2 < ns; ++e) {
         if (!r->xs[e]) HIP_TRY(hipStreamCreateWithFlags(&r->xs[e], hipStreamNonBlocking));
@@ -2953,7 +2963,7 @@ static int do_mul_relin(alch_ring* r, const alch_hint* hint, const void* a, cons
         for (size_t done = 0; done < batch; done += chunk, ++idx) {
             const size_t now = std::min(chunk, batch - done);
             const int par = (int)(idx & 1);
-            c.digits = reinterpret_cast<char*>(r->ws_digits) + (par ? dig_bytes : 0);
+            c.digits = reinterpret_cast<char*>(r->ws_digits.p) + (par ? dig_bytes : 0);
             c.a = reinterpret_cast<const W*>(a) + done * ct_words;
             c.b = reinterpret_cast<const W*>(b) + done * ct_words;
             c.out = reinterpret_cast<W*>(out) + done * ct_words;
@@ -2975,7 +2985,7 @@ static int do_mul_relin(alch_ring* r, const alch_hint* hint, const void* a, cons
         const size_t now = std::min(chunk, batch - done);
         const int lane = two ? (int)(idx % (size_t)ns) : 0;
         c.stream = lanes[lane];
-        c.digits = reinterpret_cast<char*>(r->ws_digits) + (size_t)lane * dig_bytes;
+        c.digits = reinterpret_cast<char*>(r->ws_digits.p) + (size_t)lane * dig_bytes;
         c.a = reinterpret_cast<const W*>(a) + done * ct_words;
         c.b = reinterpret_cast<const W*>(b) + done * ct_words;
         c.out = reinterpret_cast<W*>(out) + done * ct_words;
@@ -3015,21 +3025,10 @@ extern "C" int alch_ct_mul_relin(alch_ring* r, const alch_hint* hint, const alch
     int rc;
     if (flags & ALCH_POW_IN) {
         const size_t bytes = 2 * batch * elem_bytes(r);
-        if ((rc = ensure_ws(&r->ws_in, &r->ws_in_bytes, 2 * bytes)) != ALCH_OK) return rc;
-        char* wa = reinterpret_cast<char*>(r->ws_in);
-        char* wb = wa + bytes;
-        if (split_ring(r)) {                 // the split transform works in place: copy first (general-index kernels take src)
-            HIP_TRY(hipMemcpyAsync(wa, a->dptr, bytes, hipMemcpyDeviceToDevice, r->stream));
-            HIP_TRY(hipMemcpyAsync(wb, b->dptr, bytes, hipMemcpyDeviceToDevice, r->stream));
-            rc = ALCH_BY_WORD(r, do_crt, r, wa, 0, 4 * batch, false);
-        } else {                             // out of place, straight from the operands
-            rc = ALCH_BY_WORD(r, do_crt, r, wa, 0, 2 * batch, false, a->dptr);
-            if (rc == ALCH_OK)
-                rc = ALCH_BY_WORD(r, do_crt, r, wb, 0, 2 * batch, false, b->dptr);
-        }
-        if (rc != ALCH_OK) return rc;
-        pa = wa;
-        pb = wb;
+        if ((rc = r->ws_in.reserve(2 * bytes)) != ALCH_OK) return rc;
+        pa = r->ws_in.p;
+        pb = reinterpret_cast<char*>(r->ws_in.p) + bytes;
+        if ((rc = ALCH_BY_WORD(r, crt_into, r, r->ws_in.p, {a->dptr, b->dptr}, 2 * batch, false)) != ALCH_OK) return rc;
     }
     // split rings (a limb-polynomial is twice an LDS-resident transform), TrivGad: the same two-launch structure as the LDS-resident sizes
     // since round 3 (k_tensor_crtinv_split + k_ks_accum_split<FROM_OPS>); option split_fused < 2 keeps the composed forms
@@ -3057,25 +3056,17 @@ static int do_ct_mul(alch_ring* r, const void* a, const void* b, void* out, size
     size_t chunk = batch;
     int rc;
     if (pow_in) {                                          // CRT copies of one chunk's operands: 2 + 2 elements per ciphertext
-        chunk = std::min(batch, std::max<size_t>(1, (r->scratch_mib << 20) / (4 * eb)));
-        if ((rc = ensure_ws(&r->ws_in, &r->ws_in_bytes, chunk * 4 * eb)) != ALCH_OK) return rc;
+        chunk = scratch_chunk(r->scratch_mib << 20, batch, 4 * eb);
+        if ((rc = r->ws_in.reserve(chunk * 4 * eb)) != ALCH_OK) return rc;
     }
     for (size_t done = 0; done < batch; done += chunk) {
         const size_t now = std::min(chunk, batch - done);
         const W* pa = reinterpret_cast<const W*>(a) + done * 2 * ew;
         const W* pb = reinterpret_cast<const W*>(b) + done * 2 * ew;
-        if (pow_in) {
-            char* wa = reinterpret_cast<char*>(r->ws_in);
-            char* wb = wa + now * 2 * eb;
-            if (split_ring(r)) {                           // the split transform works in place: copy first
-                HIP_TRY(hipMemcpyAsync(wa, pa, now * 2 * eb, hipMemcpyDeviceToDevice, r->stream));
-                HIP_TRY(hipMemcpyAsync(wb, pb, now * 2 * eb, hipMemcpyDeviceToDevice, r->stream));
-                rc = do_crt<W>(r, wa, 0, 4 * now, false);
-            } else if ((rc = do_crt<W>(r, wa, 0, 2 * now, false, pa)) == ALCH_OK)
-                rc = do_crt<W>(r, wb, 0, 2 * now, false, pb);
-            if (rc != ALCH_OK) return rc;
-            pa = reinterpret_cast<const W*>(wa);
-            pb = reinterpret_cast<const W*>(wb);
+        if (pow_in) {                                      // both operands contiguous: on a split ring, one transform launch
+            if ((rc = crt_into<W>(r, r->ws_in.p, {pa, pb}, 2 * now, false)) != ALCH_OK) return rc;
+            pa = reinterpret_cast<const W*>(r->ws_in.p);
+            pb = pa + now * 2 * ew;
         }
         ALCH_LAUNCH_VW(k_ct_tensor3, r, now * ew, r->stream, dev_ring<W>(r), pa, pb, reinterpret_cast<W*>(out) + done * 3 * ew, now, sr2, gt);
         HIP_TRY(hipGetLastError());
@@ -3138,8 +3129,8 @@ static int do_ct_add(alch_ring* r, void* out, size_t batch, const void* a, int d
     size_t chunk = batch;
     if (col_a || col_b) {
         const size_t per_ct = ((col_a ? ea : 0) + (col_b ? ebb : 0)) * eb;
-        chunk = std::min(batch, std::max<size_t>(1, (r->scratch_mib << 20) / per_ct));
-        if (int rc = ensure_ws(&r->ws_in, &r->ws_in_bytes, chunk * per_ct)) return rc;
+        chunk = scratch_chunk(r->scratch_mib << 20, batch, per_ct);
+        if (int rc = r->ws_in.reserve(chunk * per_ct)) return rc;
     }
     const GTab<W> gt = pow_basis ? GTab<W>{} : g_table<W>(r);
     const u32 ka = pow_basis ? 0u : g_a, kb = pow_basis ? 0u : g_b;
@@ -3147,17 +3138,16 @@ static int do_ct_add(alch_ring* r, void* out, size_t batch, const void* a, int d
         const size_t now = std::min(chunk, batch - done);
         const W* pa = reinterpret_cast<const W*>(a) + done * ea * ew;
         const W* pb = deg_b ? reinterpret_cast<const W*>(b) + done * ebb * ew : nullptr;
-        char* ws = reinterpret_cast<char*>(r->ws_in);
+        char *wa = reinterpret_cast<char*>(r->ws_in.p), *wb = wa + (col_a ? now * ea * eb : 0);    // this chunk's operands, back to back
         if (col_a) {
             for (unsigned t = 0; t < g_a; ++t)
-                if (int rc = do_columns<W>(r, GEN_MULG_POW, ws, 0, now * ea, 1, nullptr, t == 0 ? pa : nullptr)) return rc;
-            pa = reinterpret_cast<const W*>(ws);
-            ws += now * ea * eb;
+                if (int rc = do_columns<W>(r, GEN_MULG_POW, wa, 0, now * ea, 1, nullptr, t == 0 ? pa : nullptr)) return rc;
+            pa = reinterpret_cast<const W*>(wa);
         }
         if (col_b) {
             for (unsigned t = 0; t < g_b; ++t)
-                if (int rc = do_columns<W>(r, GEN_MULG_POW, ws, 0, now * ebb, 1, nullptr, t == 0 ? pb : nullptr)) return rc;
-            pb = reinterpret_cast<const W*>(ws);
+                if (int rc = do_columns<W>(r, GEN_MULG_POW, wb, 0, now * ebb, 1, nullptr, t == 0 ? pb : nullptr)) return rc;
+            pb = reinterpret_cast<const W*>(wb);
         }
         W* po = reinterpret_cast<W*>(out) + done * eo * ew;
         int rc;
@@ -3219,24 +3209,21 @@ static int do_key_switch_quad(alch_ring* r, const alch_hint* hint, const void* i
     // scratch per ciphertext: c2 in both bases + the stage's digits (+ the CRT copy of a Pow-basis input)
     const size_t stage_elems = 2 + s.elems;
     const size_t per_ct = (stage_elems + (pow_in ? 3 : 0)) * eb;
-    s.chunk = std::min(batch, std::max<size_t>(1, (r->scratch_mib << 20) / per_ct));
-    int rc = ensure_ws(&r->ws_digits, &r->ws_digits_bytes, s.chunk * per_ct);
+    const size_t chunk = scratch_chunk(r->scratch_mib << 20, batch, per_ct);
+    int rc = r->ws_digits.reserve(chunk * per_ct);
     if (rc != ALCH_OK) return rc;
-    s.scratch = reinterpret_cast<char*>(r->ws_digits);
-    W* c2pow = reinterpret_cast<W*>(s.scratch);
-    W* c2crt = s.fused_digits ? reinterpret_cast<W*>(s.scratch + s.chunk * eb) : nullptr;
-    char* win = s.scratch + s.chunk * stage_elems * eb;
+    Carve cv(r->ws_digits.p, chunk);
+    ks_stage_carve(s, cv, eb);
+    char* win = cv.take(pow_in ? 3 * eb : 0);
+    if (!cv.matches(per_ct)) return fail(ALCH_E_INTERNAL, "do_key_switch_quad: the scratch carve differs from the bytes reserved per ciphertext");
+    W *c2pow = s.c2, *c2crt = s.fused_digits ? s.c2crt : nullptr;
     Scal<W> sm;
     scal_to_mont<W>(r, s_pre, 1, sm);
-    for (size_t done = 0; done < batch; done += s.chunk) {
-        const size_t now = std::min(s.chunk, batch - done);
+    for (size_t done = 0; done < batch; done += chunk) {
+        const size_t now = std::min(chunk, batch - done);
         const W* src = reinterpret_cast<const W*>(in) + done * 3 * ew;
         if (pow_in) {
-            if (split_ring(r)) {                           // the split transform works in place: copy first
-                HIP_TRY(hipMemcpyAsync(win, src, now * 3 * eb, hipMemcpyDeviceToDevice, r->stream));
-                rc = do_crt<W>(r, win, 0, 3 * now, false);
-            } else rc = do_crt<W>(r, win, 0, 3 * now, false, src);
-            if (rc != ALCH_OK) return rc;
+            if ((rc = crt_into<W>(r, win, {src}, 3 * now, false)) != ALCH_OK) return rc;
             src = reinterpret_cast<const W*>(win);
         }
         W* po = reinterpret_cast<W*>(out) + done * 2 * ew;
@@ -3298,15 +3285,14 @@ static int do_mul_full(alch_ring* rh, alch_ring* rin, alch_ring* rout, const alc
     const int dup = rh->L - rin->L, ddn = rh->L - rout->L;
     const size_t n = rh->n;
     // per pipeline: digits [chunk][L_in][n] signed | key-switched chunk [chunk][2][Lh][n] | stash [slots][ddn][n] signed
-    const size_t cap = std::max<size_t>(8, (((size_t)1 << 32) - 1) / (2 * elem_bytes(rh)) / 8 * 8);   // 32-bit byte offsets per array
-    const size_t chunk = std::min(std::min(rh->chunk, cap), (batch + 7) / 8 * 8);
+    const size_t chunk = fused_chunk(rh->chunk, 2 * elem_bytes(rh), batch);                       // 32-bit byte offsets per array
     const unsigned slots = rh->rs_slots;       // resident workgroups of k_rescale_out (each owns a stash slot)
     const size_t dig_bytes = chunk * (size_t)rin->L * n * sizeof(SW);
     const size_t ks_bytes = chunk * 2 * (size_t)rh->L * n * sizeof(W);
     // stash: one slot per resident workgroup (k_rescale_out / _lin) or the lifted residues of the whole chunk (kernel_rescale_half.hpp)
     const size_t stash_bytes = std::max<size_t>(slots, 2 * chunk) * (size_t)ddn * n * sizeof(SW);
     const size_t pipe_bytes = dig_bytes + ks_bytes + stash_bytes;
-    int rc = ensure_ws(&rh->ws_full, &rh->ws_full_bytes, 2 * pipe_bytes);
+    int rc = rh->ws_full.reserve(2 * pipe_bytes);
     if (rc != ALCH_OK) return rc;
 
     uint64_t s_eff[MAXL];                                  // s_pre times the moduli the first modSwitch adds
@@ -3331,7 +3317,7 @@ static int do_mul_full(alch_ring* rh, alch_ring* rin, alch_ring* rout, const alc
     for (size_t done = 0; done < batch; done += chunk, ++idx) {
         const size_t now = std::min(chunk, batch - done);
         const bool odd = two && (idx & 1);
-        char* base = reinterpret_cast<char*>(rh->ws_full) + (odd ? pipe_bytes : 0);
+        char* base = reinterpret_cast<char*>(rh->ws_full.p) + (odd ? pipe_bytes : 0);
         c.stream = odd ? rh->aux : rh->stream;
         c.nct = now;
         // (*) 's quadratic coefficient, scaled, crtInv, TrivGad digits -- on the operands' ring
@@ -3408,14 +3394,14 @@ static int do_mul_full_unfused(alch_ring* rh, alch_ring* rin, alch_ring* rout, c
     // forms) + rescale ping-pong (2 + 2), in ring_h elements
     KsStage<W> s = ks_stage_plan<W>(rh, hint, dup, false);
     const size_t per_ct = (2 + s.elems + 4) * eb;
-    const size_t chunk = std::min(batch, std::max<size_t>(1, (rh->scratch_mib << 20) / per_ct));
-    int rc = ensure_ws(&rh->ws_full, &rh->ws_full_bytes, chunk * per_ct);
+    const size_t chunk = scratch_chunk(rh->scratch_mib << 20, batch, per_ct);
+    int rc = rh->ws_full.reserve(chunk * per_ct);
     if (rc != ALCH_OK) return rc;
-    char* ks = reinterpret_cast<char*>(rh->ws_full);
-    s.scratch = ks + chunk * 2 * eb;
-    s.chunk = chunk;
-    char* ping = s.scratch + chunk * s.elems * eb;
-    char* pong = ping + chunk * 2 * eb;
+    Carve cv(rh->ws_full.p, chunk);
+    char* ks = cv.take(2 * eb);
+    ks_stage_carve(s, cv, eb);
+    char *ping = cv.take(2 * eb), *pong = cv.take(2 * eb);
+    if (!cv.matches(per_ct)) return fail(ALCH_E_INTERNAL, "do_mul_full_unfused: the scratch carve differs from the bytes reserved per ciphertext");
     uint64_t s_eff[MAXL];                                  // s_pre times the moduli the first modSwitch adds
     for (int j = 0; j < rin->L; ++j) s_eff[j] = up_scalar(rh, dup, j + dup, s_pre ? s_pre[j] : 1);
     scal_to_mont<W>(rin, s_eff, 2, s.sr2);
@@ -3729,14 +3715,12 @@ static int do_tunnel(const alch_tunnel* t, alch_ring* rin, const void* in, void*
     const int tun_ng = (rs->opts.tunnel_fused == 4 && 4 * (size_t)rx->n * sizeof(W) <= 65536) ? 4 : 2;     // two workgroups per CU: 64 KiB of LDS each
     // scratch per ciphertext: Pow copy of the input (2 R'-elements), x0, x1 (D coefficients each), digits (D * GD elements of rx)
     const size_t per_ct = 2 * ebr + 2 * (size_t)D * ebx + (fused ? 0 : (size_t)D * GD * ebd);
-    size_t chunk = std::max<size_t>(1, (rs->scratch_mib << 20) / per_ct);
-    chunk = std::min(chunk, batch);
-    int rc = ensure_ws(&rs->ws_full, &rs->ws_full_bytes, chunk * per_ct);
+    const size_t chunk = scratch_chunk(rs->scratch_mib << 20, batch, per_ct);
+    int rc = rs->ws_full.reserve(chunk * per_ct);
     if (rc != ALCH_OK) return rc;
-    char* win = reinterpret_cast<char*>(rs->ws_full);
-    char* x0 = win + chunk * 2 * ebr;
-    char* x1 = x0 + chunk * D * ebx;
-    char* dig = x1 + chunk * D * ebx;
+    Carve cv(rs->ws_full.p, chunk);
+    char *win = cv.take(2 * ebr), *x0 = cv.take(D * ebx), *x1 = cv.take(D * ebx), *dig = cv.take(fused ? 0 : (size_t)D * GD * ebd);
+    if (!cv.matches(per_ct)) return fail(ALCH_E_INTERNAL, "do_tunnel: the scratch carve differs from the bytes reserved per ciphertext");
     uint64_t s_eff[MAXL] = {0};
     for (int j = dup; j < L; ++j) s_eff[j] = up_scalar(rs, dup, j, s_pre ? s_pre[j] : 1);      // modSwitch up: times the added moduli
     const bool scale = s_pre != nullptr || dup > 0;
@@ -3870,14 +3854,12 @@ static int do_tunnel_pow2(const alch_tunnel* t, alch_ring* rin, const void* in, 
     const size_t wb = sizeof(W), ebr = elem_bytes(rin), pd = (size_t)n_d * wb;        // pd: one limb-polynomial at the transforms' dimension
     const size_t x0_b = c0_in_place ? 0 : (size_t)d * Lin * pd, x1_b = base2 ? (size_t)d * L * pd : 0, dig_b = (size_t)d * GD * L * pd;
     const size_t per_ct = 2 * ebr + x0_b + x1_b + dig_b;
-    size_t chunk = std::max<size_t>(1, (rs->scratch_mib << 20) / per_ct);
-    chunk = std::min(chunk, batch);
-    int rc = ensure_ws(&rs->ws_full, &rs->ws_full_bytes, chunk * per_ct);
+    const size_t chunk = scratch_chunk(rs->scratch_mib << 20, batch, per_ct);
+    int rc = rs->ws_full.reserve(chunk * per_ct);
     if (rc != ALCH_OK) return rc;
-    char* win = reinterpret_cast<char*>(rs->ws_full);
-    char* x0 = win + chunk * 2 * ebr;
-    char* x1 = x0 + chunk * x0_b;
-    char* dig = x1 + chunk * x1_b;
+    Carve cv(rs->ws_full.p, chunk);
+    char *win = cv.take(2 * ebr), *x0 = cv.take(x0_b), *x1 = cv.take(x1_b), *dig = cv.take(dig_b);
+    if (!cv.matches(per_ct)) return fail(ALCH_E_INTERNAL, "do_tunnel_pow2: the scratch carve differs from the bytes reserved per ciphertext");
     uint64_t s_eff[MAXL] = {0};
     for (int j = dup; j < L; ++j) s_eff[j] = up_scalar(rs, dup, j, s_pre ? s_pre[j] : 1);      // modSwitch up: times the added moduli
     const bool scale = s_pre != nullptr || dup > 0;
@@ -3888,12 +3870,7 @@ static int do_tunnel_pow2(const alch_tunnel* t, alch_ring* rin, const void* in, 
         const size_t now = std::min(chunk, batch - done);
         const char* src = reinterpret_cast<const char*>(in) + done * 2 * ebr;
         // Pow basis of R' (a copy: the caller's ciphertexts are left alone); Pow-basis input is read in place
-        if (!pin) {
-            if (split_ring(rin)) {                     // the split transforms work in place only
-                HIP_TRY(hipMemcpyAsync(win, src, now * 2 * ebr, hipMemcpyDeviceToDevice, rs->stream));
-                if ((rc = do_crt<W>(rin, win, 0, 2 * now, true, nullptr, rs)) != ALCH_OK) return rc;
-            } else if ((rc = do_crt<W>(rin, win, 0, 2 * now, true, src, rs)) != ALCH_OK) return rc;
-        }
+        if (!pin && (rc = crt_into<W>(rin, win, {src}, 2 * now, true, rs)) != ALCH_OK) return rc;
         const W* pow_in = reinterpret_cast<const W*>(pin ? src : win);
         W* px0 = c0_in_place ? nullptr : reinterpret_cast<W*>(x0);
         if (base2) launch_tun2_gather<W, false>(rs, d, pow_in, px0, reinterpret_cast<W*>(x1), n_d, now, sm, scale, (u32)dup);
@@ -4095,16 +4072,15 @@ extern "C" int alch_ct_automorph(const void* handle, const alch_buf* in, alch_bu
     int rc;
     const u32* tab = nullptr;
     if (r->gen && (rc = automorph_dev_table(r, a->j, &tab)) != ALCH_OK) return rc;
-    size_t chunk = std::max<size_t>(1, (r->scratch_mib << 20) / (2 * eb));
-    chunk = std::min(chunk, batch);
-    if ((rc = ensure_ws(&r->ws_auto, &r->ws_auto_bytes, chunk * 2 * eb)) != ALCH_OK) return rc;
+    const size_t chunk = scratch_chunk(r->scratch_mib << 20, batch, 2 * eb);
+    if ((rc = r->ws_auto.reserve(chunk * 2 * eb)) != ALCH_OK) return rc;
     for (size_t done = 0; done < batch; done += chunk) {
         const size_t now = std::min(chunk, batch - done);
         const char* src = reinterpret_cast<const char*>(in->dptr) + done * 2 * eb;
         char* dst = reinterpret_cast<char*>(out->dptr) + done * 2 * eb;
-        if ((rc = ALCH_BY_WORD(r, launch_automorph, r, r->ws_auto, src, 2 * now, a->j, tab)) != ALCH_OK) return rc;
-        if (a->tun->pow2) rc = ALCH_BY_WORD(r, do_tunnel_pow2, a->tun, r, r->ws_auto, dst, now, s_pre, 0u);
-        else rc = ALCH_BY_WORD(r, do_tunnel, a->tun, r, r->ws_auto, dst, now, s_pre, 0u);
+        if ((rc = ALCH_BY_WORD(r, launch_automorph, r, r->ws_auto.p, src, 2 * now, a->j, tab)) != ALCH_OK) return rc;
+        if (a->tun->pow2) rc = ALCH_BY_WORD(r, do_tunnel_pow2, a->tun, r, r->ws_auto.p, dst, now, s_pre, 0u);
+        else rc = ALCH_BY_WORD(r, do_tunnel, a->tun, r, r->ws_auto.p, dst, now, s_pre, 0u);
         if (rc != ALCH_OK) return rc;
     }
     return ALCH_OK;
@@ -4139,35 +4115,30 @@ static int do_mod_switch(alch_ring* rin, alch_ring* rout, const void* in, void* 
     if (rin->gen && rin->opts.rs_lin && ddn <= MAXDROP && !(flags & ALCH_POW_IN)) {
         // kept limbs stay in the CRT basis
         const size_t per_b = P * (size_t)ddn * n * sizeof(W);
-        size_t chunk = std::min(batch, std::max<size_t>(1, (rin->scratch_mib << 20) / per_b));
-        int rc = ensure_ws(&rin->ws_full, &rin->ws_full_bytes, chunk * per_b);
+        const size_t chunk = scratch_chunk(rin->scratch_mib << 20, batch, per_b);
+        int rc = rin->ws_full.reserve(chunk * per_b);
         if (rc != ALCH_OK) return rc;
         for (size_t done = 0; done < batch; done += chunk) {
             const size_t now = std::min(chunk, batch - done);
-            if ((rc = rescale_down_crt<W>(rin, ddn, reinterpret_cast<const char*>(in) + done * P * eb, rin->ws_full,
+            if ((rc = rescale_down_crt<W>(rin, ddn, reinterpret_cast<const char*>(in) + done * P * eb, rin->ws_full.p,
                                           reinterpret_cast<char*>(out) + done * P * elem_bytes(rout), P * now, dec_c0,
                                           (flags & ALCH_POW_OUT) != 0, P)) != ALCH_OK) return rc;
         }
         return ALCH_OK;
     }
     const size_t per_ct = 3 * P * eb;                          // Pow copy + ping + pong
-    size_t chunk = std::max<size_t>(1, (rin->scratch_mib << 20) / per_ct);
-    chunk = std::min(chunk, batch);
-    int rc = ensure_ws(&rin->ws_full, &rin->ws_full_bytes, chunk * per_ct);
+    const size_t chunk = scratch_chunk(rin->scratch_mib << 20, batch, per_ct);
+    int rc = rin->ws_full.reserve(chunk * per_ct);
     if (rc != ALCH_OK) return rc;
-    char* cur0 = reinterpret_cast<char*>(rin->ws_full);
-    char* ping = cur0 + chunk * P * eb;
-    char* pong = ping + chunk * P * eb;
+    Carve cv(rin->ws_full.p, chunk);
+    char *cur0 = cv.take(P * eb), *ping = cv.take(P * eb), *pong = cv.take(P * eb);
+    if (!cv.matches(per_ct)) return fail(ALCH_E_INTERNAL, "do_mod_switch: the scratch carve differs from the bytes reserved per ciphertext");
     const size_t in_bytes = P * eb;
     for (size_t done = 0; done < batch; done += chunk) {
         const size_t now = std::min(chunk, batch - done);
         const char* src = reinterpret_cast<const char*>(in) + done * in_bytes;
         if (flags & ALCH_POW_IN) HIP_TRY(hipMemcpyAsync(cur0, src, now * in_bytes, hipMemcpyDeviceToDevice, rin->stream));
-        else if (rin->gen || !split_ring(rin)) { if ((rc = do_crt<W>(rin, cur0, 0, P * now, true, src)) != ALCH_OK) return rc; }
-        else {                                                 // split transforms work in place
-            HIP_TRY(hipMemcpyAsync(cur0, src, now * in_bytes, hipMemcpyDeviceToDevice, rin->stream));
-            if ((rc = do_crt<W>(rin, cur0, 0, P * now, true)) != ALCH_OK) return rc;
-        }
+        else if ((rc = crt_into<W>(rin, cur0, {src}, P * now, true)) != ALCH_OK) return rc;
         if ((rc = rescale_down_limbs<W>(rin, rout, cur0, ping, pong, out, done, now, P, dec_c0, (flags & ALCH_POW_OUT) != 0)) != ALCH_OK) return rc;
     }
     return ALCH_OK;
@@ -4343,22 +4314,23 @@ template <typename W>
 static int do_decrypt(alch_ring* r, const void* in, size_t batch, int degree, const void* sk, const uint64_t* s_pre, void* out,
                       const alch_ring* rd, void* dst, uint64_t l_scalar, u64* maxd, bool pow_in) {
     const size_t per = (size_t)degree + 1, eb = elem_bytes(r);
-    const size_t units = (out ? 0 : 1) + (pow_in ? per : 0);          // scratch elements per ciphertext
+    const size_t per_ct = ((out ? 0 : 1) + (pow_in ? per : 0)) * eb;  // scratch per ciphertext: c(s), the CRT copy of a Pow-basis input
     size_t chunk = batch;
-    if (units) {
-        chunk = std::max<size_t>(1, std::min<size_t>(batch, ((size_t)1 << 30) / (units * eb)));
-        if (int rc = ensure_ws(&r->ws_lift, &r->ws_lift_bytes, chunk * units * eb)) return rc;
+    if (per_ct) {
+        chunk = scratch_chunk((size_t)1 << 30, batch, per_ct);
+        if (int rc = r->ws_lift.reserve(chunk * per_ct)) return rc;
     }
-    char* ws_in = reinterpret_cast<char*>(r->ws_lift) + (out ? 0 : chunk * eb);
+    Carve cv(r->ws_lift.p, chunk);
+    char *ws_cs = cv.take(out ? 0 : eb), *ws_in = cv.take(pow_in ? per * eb : 0);
+    if (!cv.matches(per_ct)) return fail(ALCH_E_INTERNAL, "do_decrypt: the scratch carve differs from the bytes reserved per ciphertext");
     for (size_t done = 0; done < batch; done += chunk) {
         const size_t now = std::min(chunk, batch - done);
         const char* src = reinterpret_cast<const char*>(in) + done * per * eb;
         if (pow_in) {
-            HIP_TRY(hipMemcpyAsync(ws_in, src, now * per * eb, hipMemcpyDeviceToDevice, r->stream));
-            if (int rc = do_crt<W>(r, ws_in, 0, now * per, false)) return rc;
+            if (int rc = crt_into<W>(r, ws_in, {src}, now * per, false)) return rc;
             src = ws_in;
         }
-        void* cs = out ? reinterpret_cast<char*>(out) + done * eb : r->ws_lift;
+        void* cs = out ? reinterpret_cast<char*>(out) + done * eb : ws_cs;
         if (int rc = eval_sk_dec<W>(r, src, now, degree, sk, s_pre, cs)) return rc;
         if (int rc = launch_lift<W>(r, rd, cs, dst ? reinterpret_cast<char*>(dst) + done * (size_t)r->n * 4 : nullptr,
                                     maxd ? maxd + done * (size_t)r->L : nullptr, now, l_scalar)) return rc;
@@ -4395,13 +4367,13 @@ static int check_lift_dst(const char* who, const alch_ring* r, const alch_buf* d
 static int maxd_get(alch_ring* r, const uint64_t* want, size_t count, u64** dev) {
     *dev = nullptr;
     if (!want) return ALCH_OK;
-    if (int rc = ensure_ws(&r->ws_maxd, &r->ws_maxd_bytes, count * (size_t)r->L * sizeof(u64))) return rc;
-    *dev = reinterpret_cast<u64*>(r->ws_maxd);
+    if (int rc = r->ws_maxd.reserve(count * (size_t)r->L * sizeof(u64))) return rc;
+    *dev = reinterpret_cast<u64*>(r->ws_maxd.p);
     return ALCH_OK;
 }
 static int maxd_fetch(alch_ring* r, uint64_t* host, size_t count) {
     if (!host) return ALCH_OK;
-    HIP_TRY(hipMemcpyAsync(host, r->ws_maxd, count * (size_t)r->L * sizeof(u64), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipMemcpyAsync(host, r->ws_maxd.p, count * (size_t)r->L * sizeof(u64), hipMemcpyDeviceToHost, r->stream));
     HIP_TRY(hipStreamSynchronize(r->stream));
     return ALCH_OK;
 }
@@ -4548,9 +4520,9 @@ static int do_gauss_dec(alch_ring* r, const gauss::Plan& P, void* dst, size_t co
         return ALCH_OK;
     }
     // scratch of one chunk: at most 1 GiB and fewer than 2^31 coefficients (2^27 doubles)
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(count, ((size_t)1 << 27) / n));
-    if (int rc = ensure_ws(&r->ws_gauss, &r->ws_gauss_bytes, chunk * n * sizeof(double))) return rc;
-    double* xs = reinterpret_cast<double*>(r->ws_gauss);
+    const size_t chunk = scratch_chunk((size_t)1 << 30, count, n * sizeof(double));
+    if (int rc = r->ws_gauss.reserve(chunk * n * sizeof(double))) return rc;
+    double* xs = reinterpret_cast<double*>(r->ws_gauss.p);
     for (size_t done = 0; done < count; done += chunk) {
         const size_t now = std::min(chunk, count - done);
         const u32 total = (u32)(now * n);
@@ -4788,9 +4760,9 @@ static int pt_lift_in(alch_ring* lift, void* dst, const void* src, size_t count,
 template <typename W>
 static int do_pt_mul(alch_ring* lift, const alch_ring* rp, void* dst, const void* a, const void* b, size_t count) {
     const size_t eb = elem_bytes(lift), zb = (size_t)lift->n * 4;
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(count, (lift->scratch_mib << 20) / (2 * eb)));
-    if (int rc = ensure_ws(&lift->ws_lift, &lift->ws_lift_bytes, 2 * chunk * eb)) return rc;
-    char* A = reinterpret_cast<char*>(lift->ws_lift);
+    const size_t chunk = scratch_chunk(lift->scratch_mib << 20, count, 2 * eb);
+    if (int rc = lift->ws_lift.reserve(2 * chunk * eb)) return rc;
+    char* A = reinterpret_cast<char*>(lift->ws_lift.p);
     for (size_t done = 0; done < count; done += chunk) {
         const size_t now = std::min(chunk, count - done);
         char* B = A + now * eb;                                       // both operands contiguous: one forward transform launch
@@ -4922,9 +4894,9 @@ template <typename W>
 static int do_pt_eval_lin(const alch_ptlin* f, const alch_ring* rd, const void* src, void* dst, size_t count) {
     alch_ring* lift = f->lift;
     const size_t eb = elem_bytes(lift), D = f->d_rel;
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(count, (lift->scratch_mib << 20) / ((D + 1) * eb)));
-    if (int rc = ensure_ws(&lift->ws_lift, &lift->ws_lift_bytes, chunk * (D + 1) * eb)) return rc;
-    char* X = reinterpret_cast<char*>(lift->ws_lift);
+    const size_t chunk = scratch_chunk(lift->scratch_mib << 20, count, (D + 1) * eb);
+    if (int rc = lift->ws_lift.reserve(chunk * (D + 1) * eb)) return rc;
+    char* X = reinterpret_cast<char*>(lift->ws_lift.p);
     for (size_t done = 0; done < count; done += chunk) {
         const size_t now = std::min(chunk, count - done);
         char* O = X + now * D * eb;

@@ -269,6 +269,40 @@ def test_error_term_matches_the_oracle(oracle_lib, m, L, bits, batch):
                 del out, gin
 
 
+@pytest.mark.parametrize("m,bits,split", [(1 << 12, 30, False), (1 << 16, 60, True), (1 << 17, 30, True)])
+def test_pow_in_staging_on_resident_and_split_rings(oracle_lib, m, bits, split):
+    """ALCH_POW_IN through do_decrypt's staging, the CRT copy of one chunk's input in the ring's scratch: transformed out of place,
+    straight from the caller's ciphertexts, where a limb-polynomial fits one LDS-resident transform; copied and transformed in place
+    on the split rings -- the smallest of them, n = 2^15 on 8-byte words and n = 2^16 on 4-byte words.  One limb, batch 2, degree 1:
+    alch_ct_error_term (c(s) into the caller's buffer) and alch_ct_decrypt_lift (c(s) in the scratch, next to the staged input)
+    against the C restatement and Python integers; the input is left as uploaded."""
+    qs = moduli(m, 1, bits, True)
+    ring = A.Ring(m, qs)
+    assert ring.word_bytes == (4 if bits <= 31 else 8)
+    assert (ring.n.bit_length() - 1 > (15 if ring.word_bytes == 4 else 14)) == split        # split_ring
+    O, general = oracle_ring(oracle_lib, m, qs)
+    batch, q = 2, qs[0]
+    rng = np.random.default_rng(m + bits)
+    sk, cts = rand_elems(rng, 1, ring.n, qs), rand_elems(rng, 2 * batch, ring.n, qs)
+    want = [oracle_error_term(O, general, [cts[2 * b], cts[2 * b + 1]], sk[0], None) for b in range(batch)]
+    src = np.stack([O.crtinv(np.ascontiguousarray(c)) for c in cts])
+    gin, gsk, out = ring.upload(src), ring.upload(sk), ring.alloc(batch)
+    D.error_term(gin, batch, gsk, degree=1, flags=capi.ALCH_POW_IN, out=out)
+    got = out.download()
+    for b in range(batch):
+        assert np.array_equal(got[b], want[b]), (m, b)
+    p = primes_1_mod(m, 1, 1 << 24)[0]                  # a ring of its own for the lift: no nocrt ring exists at n = 2^16
+    zp = A.Ring(m, [p])
+    dst = zp.alloc(batch)
+    digits = D.decrypt_lift(gin, batch, gsk, dst=dst, l=1, want_max=True, flags=capi.ALCH_POW_IN)
+    low = dst.download()
+    for b in range(batch):
+        lifted = [centred(int(v), q) for v in want[b][:, 0]]
+        assert low[b, :, 0].tolist() == [v % p for v in lifted], (m, b)
+        assert digits[b] == to_digits(max(abs(v) for v in lifted), qs), (m, b)
+    assert np.array_equal(gin.download(), src)
+
+
 def decrypt_lift_case(oracle_lib, m, L, bits, balanced, word_bytes):
     qs = moduli(m, L, bits, balanced)
     ring = A.Ring(m, qs)

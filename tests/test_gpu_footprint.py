@@ -59,7 +59,8 @@ Families, the kernels their rows reach and how that is established:
      38400 -> 25600 under scratch_mib 1 (chunks of 2, 2, 1), 64 -> 32 with both gadgets and 2^12 -> 2^13 under scratch_mib 1 (11 = 8 + 3);
      whether a pair may have the E' ring is asserted from alch_tunnel_create's condition, pieces_ok is what
      tests/test_tunnel_table_host.py asserts for the same pair.  Every scratch_mib row restates its walk's bytes per ciphertext and
-     asserts (source_has) that the restated expression still stands in alchemy_hip.hip.
+     asserts (source_has) that the restated expression, the walk's call of scratch_chunk and that rule's body (scratch_plan.hpp) still
+     stand in the sources.
   4e. test_decrypt_side   alch_ct_error_term, alch_buf_lift, alch_ct_decrypt_lift: degree 1 and 2, L = 1, 3, 8, n = 32 (a wavefront per
      element), 256 and 2048 (a workgroup per element), index 45; batch 5 and 3.
   4f. test_between_index_methods      alch_buf_embed / _twace on the three bases and alch_buf_coeffs for (9, 45) and (32, 96).
@@ -151,13 +152,18 @@ def source_constants():
 
 @functools.lru_cache(maxsize=None)
 def lib_source():
-    return open(os.path.join(CSRC, "alchemy_hip.hip")).read()
+    return open(os.path.join(CSRC, "alchemy_hip.hip")).read() + open(os.path.join(CSRC, "scratch_plan.hpp")).read()
+
+
+# the one rule every walk's chunk comes from (scratch_plan.hpp); the rows pin their walk's call of it and its bytes per item
+SCRATCH_CHUNK = ("inline size_t scratch_chunk(size_t budget_bytes, size_t batch, size_t per_item_bytes) {\n"
+                 "    return std::min(batch, std::max<size_t>(1, budget_bytes / per_item_bytes));\n}")
 
 
 def source_has(*expressions):
     """The chunk sizes below restate what the library computes; each restated expression must still stand in the source, so that a
     retune of a walk's scratch per ciphertext fails here and names the rows to resize."""
-    for e in expressions:
+    for e in (SCRATCH_CHUNK,) + expressions:
         assert e in lib_source(), e
 
 
@@ -659,7 +665,7 @@ def test_mul_relin(oracle_lib, row):
         fused = word == 4 and ring.n <= gen_ks_bound() and opts.get("gen_fused", 1)         # gen_ks_fused
         assert bool(fused) == ("fused" in row) and (ring.n > gen_ks_bound()) == (m == 21609)
         source_has(KS_STAGE_ELEMS, "const size_t per_ct = s.elems * elem_bytes(r);",
-                   "s.chunk = std::min(batch, std::max<size_t>(1, (r->scratch_mib << 20) / per_ct));")
+                   "const size_t chunk = scratch_chunk(r->scratch_mib << 20, batch, per_ct);")
         chunk = (1 << 20) // ((2 + (0 if fused else ring.L)) * ring.n * ring.L * word)      # ks_stage_plan's elems, do_mul_relin_unfused's chunk
         assert (chunk >= batch) if fused else (chunk == (2 if word == 4 else 1) and batch % 2 == 1)   # 4-byte words: a ragged last chunk
     else:
@@ -730,7 +736,7 @@ def test_ct_mul(oracle_lib, row):
     if row[0] == "w":
         assert (ring.n.bit_length() - 1 > source_constants()["split_above"][8]) == (row == "w15")
     if pow_row:
-        source_has("chunk = std::min(batch, std::max<size_t>(1, (r->scratch_mib << 20) / (4 * eb)));")       # do_ct_mul, pow_in
+        source_has("chunk = scratch_chunk(r->scratch_mib << 20, batch, 4 * eb);")       # do_ct_mul, pow_in
         chunk = (1 << 20) // (4 * ring.n * ring.L * ring.word_bytes)
         assert chunk == 2 and batch % chunk == 1
     (outs, as_, bs), total = gapped([3 * batch, 2 * batch, 2 * batch])
@@ -766,7 +772,7 @@ def test_key_switch_quad(oracle_lib, row):
     if "chunks" in row:
         # do_key_switch_quad: have_c2, so ks_stage_plan's elems are the L digits; CRT input
         source_has(KS_STAGE_ELEMS, "const size_t stage_elems = 2 + s.elems;", "const size_t per_ct = (stage_elems + (pow_in ? 3 : 0)) * eb;",
-                   "s.chunk = std::min(batch, std::max<size_t>(1, (r->scratch_mib << 20) / per_ct));")
+                   "const size_t chunk = scratch_chunk(r->scratch_mib << 20, batch, per_ct);")
         chunk = max(1, (1 << 20) // ((2 + ring.L) * ring.n * ring.L * 4))
         assert chunk < batch and (batch % chunk or chunk == 1) and (chunk > 1) == (row == "p11_chunks")
     hint_host = words(700 + len(row), 2 * ring.L, ring.n, qs)
@@ -829,7 +835,7 @@ def test_mul_full(oracle_lib, row):
         assert opts["chunk"] < batch < 2 * opts["chunk"] and opts["rs_slots"] < 2 * (batch - opts["chunk"])
     if "unfused" in row:                                                         # (2 + elems + 4) hint-ring elements per ciphertext
         source_has(KS_STAGE_ELEMS, "const size_t per_ct = (2 + s.elems + 4) * eb;",
-                   "const size_t chunk = std::min(batch, std::max<size_t>(1, (rh->scratch_mib << 20) / per_ct));")
+                   "const size_t chunk = scratch_chunk(rh->scratch_mib << 20, batch, per_ct);")
         assert (1 << 20) // ((2 + 4) * n * L * word) == 0                         # even without s.elems: below one ciphertext, one per chunk
     g = capi.ALCH_GAD_BASE2 if gadget == "base2" else capi.ALCH_GAD_TRIV
     hint_host = words(900 + len(row), 2 * rh.gadget_digits(g), n, qs_h)
@@ -950,8 +956,8 @@ def test_mod_switch(oracle_lib, row):
     per, gen = degree + 1, m & (m - 1) != 0
     eb = big.n * big.L * 4
     if "scratch_mib" in opts:                                                     # which walk, and how it cuts the batch
-        source_has("const size_t per_b = P * (size_t)ddn * n * sizeof(W);", "(rin->scratch_mib << 20) / per_b));",
-                   "const size_t per_ct = 3 * P * eb;", "size_t chunk = std::max<size_t>(1, (rin->scratch_mib << 20) / per_ct);")
+        source_has("const size_t per_b = P * (size_t)ddn * n * sizeof(W);", "const size_t chunk = scratch_chunk(rin->scratch_mib << 20, batch, per_b);",
+                   "const size_t per_ct = 3 * P * eb;", "const size_t chunk = scratch_chunk(rin->scratch_mib << 20, batch, per_ct);")
         lin = gen and opts.get("rs_lin", 1)
         chunk = max(1, (1 << 20) // (per * drop * big.n * 4 if lin else 3 * per * eb))
         assert chunk < batch and (batch % chunk or chunk == 1), (chunk, batch)
@@ -1024,7 +1030,7 @@ def test_tunnel(oracle_lib, row):
     ep, d_rel = A.Tunnel.info(gr, gs)
     if row == "g38400to25600_chunks":
         source_has("const size_t per_ct = 2 * ebr + 2 * (size_t)D * ebx + (fused ? 0 : (size_t)D * GD * ebd);",
-                   "size_t chunk = std::max<size_t>(1, (rs->scratch_mib << 20) / per_ct);")
+                   "const size_t chunk = scratch_chunk(rs->scratch_mib << 20, batch, per_ct);")
         ebr, ebx = L * gr.n * 4, L * 5120 * 4                                 # do_tunnel: Pow copy of the input, x0, x1, digits at phi(e') = 5120
         assert gr.n == 10240 and d_rel == 2 and (1 << 20) // (2 * ebr + 2 * d_rel * ebx + d_rel * L * ebx) == 2 and batch % 2
     if row == "p4096to8192_chunks":
@@ -1250,7 +1256,7 @@ def test_pt_mul(m, p, batch, mib):
     assert (r.n % 4 == 0) == (m != 9)
     if mib:
         lift.set_option("scratch_mib", mib)
-        source_has("std::min<size_t>(count, (lift->scratch_mib << 20) / (2 * eb)));")                 # do_pt_mul
+        source_has("const size_t chunk = scratch_chunk(lift->scratch_mib << 20, count, 2 * eb);")                 # do_pt_mul
         chunk = (1 << 20) // (2 * lift.n * lift.L * lift.word_bytes)
         assert chunk > 1 and batch > 2 * chunk and batch % chunk
     (as_, bs, ds), total = gapped([batch] * 3)
@@ -1282,7 +1288,7 @@ def test_pt_eval_lin(r_, s_, p, batch, mib):
     rr, rs, lift = A.Ring(r_, [p], nocrt=True), A.Ring(s_, [p], nocrt=True), lift_two31(s_)
     if mib:
         lift.set_option("scratch_mib", mib)
-        source_has("std::min<size_t>(count, (lift->scratch_mib << 20) / ((D + 1) * eb)));")           # do_pt_eval_lin; d_rel = 1 here
+        source_has("const size_t chunk = scratch_chunk(lift->scratch_mib << 20, count, (D + 1) * eb);")           # do_pt_eval_lin; d_rel = 1 here
         chunk = (1 << 20) // (2 * lift.n * lift.L * lift.word_bytes)
         assert chunk > 1 and batch > 2 * chunk and batch % chunk
     E, R, S = G.Index(math.gcd(r_, s_)), G.Index(r_), G.Index(s_)
