@@ -243,10 +243,33 @@ static std::recursive_mutex& device_mutex(int dev) {
 #define ALCH_CAT2(a, b) a##b
 #define ALCH_CAT(a, b) ALCH_CAT2(a, b)
 #ifndef ALCH_NO_DEVICE_LOCK
-#define ALCH_DEVICE_LOCK(dev) std::lock_guard<std::recursive_mutex> ALCH_CAT(_alch_dev_lock_, __LINE__)(device_mutex(dev))
+// How often THIS thread holds the lock of a device (the array mirrors device_mutex).  The helpers that own shared ring state -- the
+// scratch element, the extension and automorphism table caches, the pinned slots and ws_host -- take no lock of their own: they run
+// inside an entry point's, and refuse to run outside one (ALCH_REQUIRE_DEVICE_LOCK).  A caller that forgot its BIND then fails every
+// call, single-threaded ones included, instead of racing once in a while.
+static int& device_lock_depth(int dev) {
+    static thread_local int depth[64];
+    return depth[(dev >= 0 && dev < 64) ? dev : 0];
+}
+struct DeviceLock {
+    std::recursive_mutex& mu;
+    int& depth;
+    explicit DeviceLock(int dev) : mu(device_mutex(dev)), depth(device_lock_depth(dev)) { mu.lock(); ++depth; }
+    ~DeviceLock() { --depth; mu.unlock(); }
+    DeviceLock(const DeviceLock&) = delete;
+    DeviceLock& operator=(const DeviceLock&) = delete;
+};
+static inline bool device_lock_held(int dev) { return device_lock_depth(dev) > 0; }
+#define ALCH_DEVICE_LOCK(dev) DeviceLock ALCH_CAT(_alch_dev_lock_, __LINE__)(dev)
 #else
+static inline bool device_lock_held(int) { return true; }
 #define ALCH_DEVICE_LOCK(dev) ((void)0)   // tests/test_gpu_threads.py's self-test only (tools/build_variant.sh nolock): never in a product build
 #endif
+#define ALCH_REQUIRE_DEVICE_LOCK(ringp, who)                                                            \
+    do {                                                                                                \
+        if (!device_lock_held((ringp)->device))                                                         \
+            return fail(ALCH_E_INTERNAL, std::string(who) + ": device lock not held");                  \
+    } while (0)
 #define BIND(ringp)                                                                                     \
     ALCH_DEVICE_LOCK((ringp)->device);                                                                  \
     do {                                                                                                \
@@ -1677,6 +1700,8 @@ extern "C" int alch_ring_set_rng_key(alch_ring* r, const void* key) try {
     return ALCH_OK;
 } catch (...) { return abi_catch(); }
 
+// No lock (as alch_ring_device): the Haskell host imports both `unsafe`, a call that must never wait.  One aligned word is read; a host
+// that changes a ring's key or stream on one thread and asks for it on another orders the two itself.
 extern "C" int alch_ring_rng(const alch_ring* r) try {
     if (!r) return fail(ALCH_E_INVALID, "null ring");
     return r->rng_keyed ? ALCH_RNG_CHACHA20 : ALCH_RNG_SPLITMIX;
@@ -1719,6 +1744,7 @@ extern "C" int alch_ring_set_stream(alch_ring* r, void* s) try {
 
 extern "C" int alch_ring_set_option(alch_ring* r, const char* name, long value) try {
     if (!r || !name) return fail(ALCH_E_INVALID, "null argument");
+    ALCH_DEVICE_LOCK(r->device);                                      // a call in flight on another thread reads the options under this lock
     const std::string k(name);
     if (k == "chunk") { if (value < 8) return fail(ALCH_E_INVALID, "chunk must be >= 8"); r->chunk = (size_t)value; }
     else if (k == "one_stream") r->one_stream = value != 0;
@@ -2006,6 +2032,7 @@ extern "C" int alch_ring_device(const alch_ring* r, int* device, void** hip_stre
 
 template <typename W>
 static int do_transfer(alch_ring* r, void* dev, size_t count, int64_t* host, bool to_device) {
+    ALCH_REQUIRE_DEVICE_LOCK(r, "do_transfer");                       // ws_host, pin[], pin_next
     const size_t bytes = count * elem_words(r) * sizeof(int64_t);
     int rc = r->ws_host.reserve(bytes);
     if (rc != ALCH_OK) return rc;
@@ -2165,8 +2192,10 @@ extern "C" int alch_buf_checksum_at(const alch_buf* b, size_t first, size_t coun
 struct ScratchBuf {
     alch_buf* b = nullptr;
 };
+// The caller holds the device lock from here until it has finished with the element: a second thread's request may replace it
+// (alch_buf_free of the old one), and its upload would land on the words this one is about to download.
 static int scratch_get(alch_ring* r, size_t n_elems, alch_buf** out) {
-    BIND(r);
+    ALCH_REQUIRE_DEVICE_LOCK(r, "scratch_get");
     if (r->scratch && r->scratch->n_elems >= n_elems) { *out = r->scratch; return ALCH_OK; }
     if (r->scratch) { alch_buf* old = r->scratch; r->scratch = nullptr; alch_buf_free(old); }
     int rc = alch_buf_alloc(r, n_elems, &r->scratch);
@@ -2177,6 +2206,7 @@ static int scratch_get(alch_ring* r, size_t n_elems, alch_buf** out) {
 
 static int host_unary(alch_ring* r, int64_t* data, int which) {
     if (!r || !data) return fail(ALCH_E_INVALID, "null argument");
+    BIND(r);
     ScratchBuf s;
     int rc = scratch_get(r, 1, &s.b);
     if (rc != ALCH_OK) return rc;
@@ -2190,6 +2220,7 @@ extern "C" int alch_crtinv(alch_ring* r, int64_t* data) try { return host_unary(
 
 static int host_binary(alch_ring* r, int64_t* a, const int64_t* b, int op) {
     if (!r || !a || !b) return fail(ALCH_E_INVALID, "null argument");
+    BIND(r);
     ScratchBuf s;
     int rc = scratch_get(r, 2, &s.b);
     if (rc != ALCH_OK) return rc;
@@ -2232,6 +2263,7 @@ static int do_scale(alch_ring* r, void* dst, const void* src, size_t count, cons
 
 extern "C" int alch_scale(alch_ring* r, int64_t* a, const uint64_t* s) try {
     if (!r || !a || !s) return fail(ALCH_E_INVALID, "null argument");
+    BIND(r);
     ScratchBuf t;
     int rc = scratch_get(r, 1, &t.b);
     if (rc != ALCH_OK) return rc;
@@ -2248,6 +2280,7 @@ static int host_g(alch_ring* r, int64_t* a, int basis, int which /* 0 mulG, 1 di
     if (!r || !a) return fail(ALCH_E_INVALID, "null argument");
     if (basis == ALCH_BASIS_CRT && !r->has_crt) return fail(ALCH_E_NO_CRT, "this ring has no CRT basis");
     if (!r->gen || r->gh.rad == 1) return ALCH_OK;                    // two-power index: g = 1, L = identity
+    BIND(r);
     ScratchBuf s;
     int rc = scratch_get(r, 1, &s.b);
     if (rc != ALCH_OK) return rc;
@@ -2269,6 +2302,7 @@ extern "C" int alch_linv(alch_ring* r, int64_t* a) try { return host_g(r, a, ALC
 
 extern "C" int alch_decompose_triv(alch_ring* r, const int64_t* c_pow, int64_t* digits) try {
     if (!r || !c_pow || !digits) return fail(ALCH_E_INVALID, "null argument");
+    BIND(r);
     ScratchBuf s;
     int rc = scratch_get(r, 1 + (size_t)r->L, &s.b);
     if (rc != ALCH_OK) return rc;
@@ -2320,6 +2354,7 @@ static int decompose_baseb(alch_ring* r, u32 w, const int64_t* c_pow, int64_t* d
     if (n_digits) *n_digits = D;
     if (!digits) return ALCH_OK;
     if (!c_pow) return fail(ALCH_E_INVALID, "null argument");
+    BIND(r);                                                          // the n_digits-only query above reads immutable members
     ScratchBuf s;
     int rc = scratch_get(r, 1 + (size_t)D, &s.b);
     if (rc != ALCH_OK) return rc;
@@ -2411,6 +2446,7 @@ extern "C" int alch_hint_load(alch_ring* r, int gadget, const int64_t* host_crt,
     if (!r || !host_crt || !out) return fail(ALCH_E_INVALID, "null argument");
     if (gadget_width(gadget) < 0) return fail(ALCH_E_INVALID, "alch_hint_load: unknown gadget");
     const size_t elems = 2 * (size_t)gadget_digits(r, gadget);
+    BIND(r);                                                          // held across the closing synchronisation: the scratch is read until then
     ScratchBuf s;
     int rc = scratch_get(r, elems, &s.b);
     if (rc != ALCH_OK) return rc;
@@ -2556,8 +2592,9 @@ extern "C" int alch_buf_linv(alch_buf* b, size_t first, size_t count) try { retu
 extern "C" int alch_ring_share_stream(alch_ring* r, alch_ring* with) try {
     if (!r || !with) return fail(ALCH_E_INVALID, "null ring");
     if (r->device != with->device) return fail(ALCH_E_INVALID, "alch_ring_share_stream: the rings live on different devices");
-    if (r == with || r->stream == with->stream) return ALCH_OK;
-    BIND(r);
+    if (r == with) return ALCH_OK;
+    BIND(r);                                                          // one device, one lock: both rings' stream members are read under it
+    if (r->stream == with->stream) return ALCH_OK;
     HIP_TRY(hipStreamSynchronize(r->stream));
     r->stream_owner = with->stream_owner;          // releases r's own stream (destroyed with its last user), keeps with's alive
     r->stream = with->stream;
@@ -3959,6 +3996,7 @@ extern "C" int alch_automorph_table(uint32_t m, uint32_t j, uint32_t* out, size_
 // oldest leaves after the stream has drained (a queued gather may still read it).
 constexpr size_t AUTOTAB_MAX = 64;
 static int automorph_dev_table(alch_ring* r, u32 j, const u32** out) {
+    ALCH_REQUIRE_DEVICE_LOCK(r, "automorph_dev_table");
     for (auto& e : r->autotab) if (e.first == j) { *out = e.second; return ALCH_OK; }
     automorph::Plan P;
     std::vector<uint32_t> t;

@@ -97,11 +97,16 @@ static int ext_tables(alch_ring* small, alch_ring* big, const ExtTab** out) {
     if (small->L != big->L || small->word != big->word || small->zdom != big->zdom) return fail(ALCH_E_INVALID, "both rings must have the same moduli");
     for (int j = 0; j < small->L; ++j) if (small->q[j] != big->q[j]) return fail(ALCH_E_INVALID, "both rings must have the same moduli");
     if (small->device != big->device) return fail(ALCH_E_INVALID, "both rings must live on the same device");
+    // The lock comes BEFORE the scan: two first users of a pair would both miss, both build and both insert (the duplicate's device
+    // tables leak), and an insert moves the deque's map under a third thread's scan.  One device, so one lock covers both rings.  The
+    // callers use *out after this lock is gone: a deque keeps references to its elements valid across emplace_back, entries leave
+    // only with the ring, and their words are written once, below -- the scan and the insert are what needs the lock.
+    BIND(big);
+    ALCH_REQUIRE_DEVICE_LOCK(big, "ext_tables");
     for (auto& e : big->ext) if (e.first == small->m) { *out = &e.second; return ALCH_OK; }
     ExtHost h;
     int rc = ext_host_tables(small->m, big->m, h);
     if (rc != ALCH_OK) return rc;
-    BIND(big);
     ExtTab t;
     t.d_rel = h.d_rel; t.fibre = h.fibre;
     auto up = [&](int32_t** dst, const std::vector<int32_t>& v) {
