@@ -8,7 +8,8 @@ compiled code too).  There is no CPU fallback: importing works anywhere, but eve
 call raises unless the HIP library is built and a gfx950 device is present.
 """
 from .capi import AlchemyError, Buf, Hint, Ring, Tunnel, lib_path, load_library  # noqa: F401
-from .automorph import Automorph, automorph_hint, automorph_table, buf_automorph, ct_automorph  # noqa: F401
+from .automorph import (Automorph, AutomorphSet, automorph_hint, automorph_set_hints, automorph_table, buf_automorph,  # noqa: F401
+                        ct_automorph, ct_automorph_hoisted)
 from .ctadd import CtMeta, align, ct_add, ct_add_raw, ct_neg, ct_sub  # noqa: F401
 from .decrypt import decrypt_batch, decrypt_lift, digits_to_int, error_rates, error_term, lift  # noqa: F401
 from .encrypt import ct_encrypt, encrypt_batch, gauss_dec, gauss_plan, gauss_table, gen_sk  # noqa: F401

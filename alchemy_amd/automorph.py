@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import ALCH_GAD_TRIV, Buf, Ring, _check, _pu64, load_library
+from .capi import ALCH_AUTO_SUM, ALCH_GAD_TRIV, Buf, Ring, _check, _pu64, load_library
 from .hints import ks_hint
 
 
@@ -68,4 +68,50 @@ def ct_automorph(auto: Automorph, ct: Buf, batch: int, s_pre=None, out: Buf | No
         out = auto.ring.alloc(max(1, 2 * batch))
     sp = _pu64(s_pre) if s_pre is not None else None
     _check(auto.ring._l.alch_ct_automorph(auto._h, ct._h, out._h, batch, sp, flags))
+    return out if meta is None else (out, meta)
+
+
+# ---- hoisted automorphisms: several sigma_j of one batch at one gadget decomposition (include/alchemy_hip.h, "Hoisted automorphisms")
+def automorph_set_hints(ring: Ring, sk_crt: Buf, js, gadget: int = ALCH_GAD_TRIV, svar: float = 1.0, seed: int = 0) -> Buf:
+    """One buffer holding the len(js) hints one after the other, 2 * D elements each: hint r is automorph_hint(.., js[r], ..) on seed
+    `seed + 2 r` (a hint draws from its seed and the next one)."""
+    D = ring.gadget_digits(gadget)
+    out = ring.alloc(max(1, 2 * D * len(js)))
+    for r, j in enumerate(js):
+        h = automorph_hint(ring, sk_crt, j % ring.m, gadget, svar, seed + 2 * r)
+        out.copy_from(h, 2 * D, 2 * D * r, 0)
+    return out
+
+
+class AutomorphSet:
+    """alch_automorph_set: up to 32 units with their hints (copied: `ks_crt` may be reused), for ct_automorph_hoisted."""
+
+    def __init__(self, ring: Ring, js, ks_crt: Buf, gadget: int = ALCH_GAD_TRIV):
+        self.ring, self.js, self.gadget = ring, [j % ring.m for j in js], gadget
+        arr = (C.c_uint32 * max(1, len(js)))(*[j % (1 << 32) for j in js])
+        h = C.c_void_p()
+        _check(ring._l.alch_automorph_set_create(ring._h, len(js), arr, gadget, ks_crt._h, C.byref(h)))
+        self._h = h
+
+    def free(self):
+        if getattr(self, "_h", None):
+            if getattr(self.ring, "_h", None):                  # see Buf.free
+                self.ring._l.alch_automorph_set_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def ct_automorph_hoisted(aset: AutomorphSet, ct: Buf, batch: int, s_pre=None, out: Buf | None = None, sum: bool = False, meta=None):
+    """out[r * batch + b] = keySwitch(sigma_(j_r)(ct[b])) for every unit of the set at ONE decomposition of the batch; sum=True:
+    out[b] = sum_r of those (ALCH_AUTO_SUM).  Linear ciphertexts (k = 0), CRT basis in and out; s_pre as in ct_automorph.  Returns the
+    result buffer (a new one unless `out` is given), or (buffer, meta) when a CtMeta is passed (unchanged, as in ct_automorph)."""
+    if out is None:
+        out = aset.ring.alloc(max(1, 2 * batch * (1 if sum else len(aset.js))))
+    sp = _pu64(s_pre) if s_pre is not None else None
+    _check(aset.ring._l.alch_ct_automorph_hoisted(aset._h, ct._h, out._h, batch, sp, ALCH_AUTO_SUM if sum else 0))
     return out if meta is None else (out, meta)

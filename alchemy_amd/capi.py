@@ -13,6 +13,7 @@ ALCH_OK = 0
 ALCH_E_INVALID, ALCH_E_NOT_PRIME, ALCH_E_NO_CRT, ALCH_E_UNSUPPORTED = -1, -2, -3, -4
 ALCH_E_NO_DEVICE, ALCH_E_HIP, ALCH_E_NOMEM, ALCH_E_INTERNAL = -5, -6, -7, -8
 ALCH_POW_IN, ALCH_POW_OUT = 1, 2
+ALCH_AUTO_SUM = 4                                            # alch_ct_automorph_hoisted: the sum over the set's rotations
 ALCH_GAD_TRIV, ALCH_GAD_BASE2 = 0, 1
 ALCH_RNG_SPLITMIX, ALCH_RNG_CHACHA20 = 0, 1
 
@@ -54,6 +55,7 @@ SYMBOLS = [
     "alch_gadget_digits", "alch_decompose_baseb",
     "alch_ring_set_rng_key", "alch_ring_rng", "alch_rng_words",
     "alch_automorph_table", "alch_buf_automorph", "alch_automorph_create", "alch_automorph_free", "alch_ct_automorph",
+    "alch_automorph_set_create", "alch_automorph_set_free", "alch_ct_automorph_hoisted",
 ]
 
 
@@ -205,6 +207,9 @@ def load_library():
         "alch_automorph_create": [VP, C.c_uint32, C.c_int, VP, C.POINTER(VP)],
         "alch_automorph_free": [VP],
         "alch_ct_automorph": [VP, VP, VP, C.c_size_t, PU64, C.c_uint],
+        "alch_automorph_set_create": [VP, C.c_uint32, C.POINTER(C.c_uint32), C.c_int, VP, C.POINTER(VP)],
+        "alch_automorph_set_free": [VP],
+        "alch_ct_automorph_hoisted": [VP, VP, VP, C.c_size_t, PU64, C.c_uint],
     }
     for name, args in sig.items():
         fn = getattr(l, name, None)

@@ -1326,6 +1326,7 @@ __global__ void k_checksum(const W* data, size_t words, u64* sum, u64 w0) {
 #include "kernel_plain.hpp"
 #include "kernel_rlwe.hpp"
 #include "kernel_automorph.hpp"
+#include "kernel_hoist.hpp"
 
 static inline unsigned ew_grid(size_t items) {
     size_t g = (items + 255) / 256;
@@ -3722,6 +3723,26 @@ extern "C" int alch_tunnel_free(alch_tunnel* t) try {
     return ALCH_OK;
 } catch (...) { return abi_catch(); }
 
+// The digit tail of a general-index key-switch stage (do_tunnel, do_hoisted): `coeffs` embedded coefficients in x1 ([coeff][Lx][n], the
+// limbs xoff .. xoff + Lx - 1) at the transforms' ring rx, queued on rs's stream; dig receives the crt of their GD digits each,
+// decomposed and reduced in the transforms' loader -- BaseBGad 2^bw (bw > 0; examples/Tunnel.hs:24) or TrivGad (GD = Lx).
+template <typename W>
+static int gen_digit_tail(alch_ring* rs, alch_ring* rx, const char* x1, char* dig, size_t coeffs, u32 GD, u32 Lx, u32 xoff, u32 bw,
+                          const Scal<u32>& b2first, const Scal<u32>& b2kd) {
+    GenCall<W> g{};
+    g.ring = &dev_ring<W>(rx); g.gen = &gen_dev<W>(rx); g.stream = rs->stream;
+    g.src = reinterpret_cast<const W*>(x1); g.data = reinterpret_cast<W*>(dig);
+    if (bw > 0) {
+        g.op = GEN_CRT_BASE2;
+        g.npoly = coeffs * (size_t)GD * (size_t)rs->L; g.b2_first = b2first; g.b2_kd = b2kd; g.b2_D = GD; g.b2_w = bw;
+        return launch(g, "tunnel base2 crt_digits");
+    }
+    g.op = GEN_CRT_DIGITS;
+    g.npoly = coeffs * (size_t)Lx * (size_t)rs->L; g.balanced = rs->balanced; g.with_diag = true;
+    g.src_limbs = (int)Lx; g.src_first = (int)xoff;
+    return launch(g, "tunnel crt_digits");
+}
+
 // SymmSHE.tunnel on a batch of linear ciphertexts (k = 0):  out = (f'(c0), 0) + sum_i switch(hint_i, embed(c1_i)).
 // rin: the ring the ciphertexts live in -- the tunnel's R' ring or its last limbs (PT2CT emits modSwitch_ .: tunnel_ hint .: modSwitch_,
 // PT2CT.hs:224-229; the leading modSwitch up, x -> (0, q_a x), is then folded in: the added limbs are zero, so neither their
@@ -3764,8 +3785,6 @@ static int do_tunnel(const alch_tunnel* t, alch_ring* rin, const void* in, void*
     Scal<W> sm;
     scal_to_mont<W>(rs, s_eff, 1, sm);
     const bool dec_c0 = rr->gh.rad > 1 && t->linv_skip_mask != ((1u << rr->gh.nfact) - 1);
-    GenCall<W> gx{};                                 // what the pass-engine launches on rx share
-    gx.ring = &dev_ring<W>(rx); gx.gen = &gen_dev<W>(rx); gx.stream = rs->stream;
     for (size_t done = 0; done < batch; done += chunk) {
         const size_t now = std::min(chunk, batch - done);
         const char* src = reinterpret_cast<const char*>(in) + done * 2 * ebr;
@@ -3815,18 +3834,7 @@ static int do_tunnel(const alch_tunnel* t, alch_ring* rin, const void* in, void*
             }
             continue;
         }
-        if (base2) {                                 // BaseBGad 2 (examples/Tunnel.hs:24): decompose + reduce in the transforms' loader
-            GenCall<W> g = gx;
-            g.op = GEN_CRT_BASE2; g.src = reinterpret_cast<const W*>(x1); g.data = reinterpret_cast<W*>(dig);
-            g.npoly = now * (size_t)D * (size_t)GD * (size_t)L; g.b2_first = b2first; g.b2_kd = b2kd; g.b2_D = GD; g.b2_w = bw;
-            if ((rc = launch(g, "tunnel base2 crt_digits")) != ALCH_OK) return rc;
-        } else {
-            GenCall<W> g = gx;
-            g.op = GEN_CRT_DIGITS; g.src = reinterpret_cast<const W*>(x1); g.data = reinterpret_cast<W*>(dig);
-            g.npoly = now * (size_t)D * (size_t)Lx * (size_t)L; g.balanced = rs->balanced; g.with_diag = true;
-            g.src_limbs = (int)Lx; g.src_first = (int)xoff;
-            if ((rc = launch(g, "tunnel crt_digits")) != ALCH_OK) return rc;
-        }
+        if ((rc = gen_digit_tail<W>(rs, rx, x1, dig, now * (size_t)D, GD, Lx, xoff, bw, b2first, b2kd)) != ALCH_OK) return rc;
         if (mac_e) {
             if constexpr (sizeof(W) == 4) {
                 const size_t pieces = (now + 3) / 4 * (size_t)rs->L * (rs->n / 4);
@@ -3864,6 +3872,34 @@ static void launch_tun2_gather(alch_ring* rs, u32 d, const W* in, W* x0, W* dst1
     if (g == 1) hipLaunchKernelGGL((k_tun2_gather<W, 1, TRIV>), grid, block, 0, rs->stream, dev_ring<W>(rs), in, x0, dst1, d, n_d, nct, sm, sc, dup, bal);
     else if (g == 2) hipLaunchKernelGGL((k_tun2_gather<W, 2, TRIV>), grid, block, 0, rs->stream, dev_ring<W>(rs), in, x0, dst1, d, n_d, nct, sm, sc, dup, bal);
     else hipLaunchKernelGGL((k_tun2_gather<W, VL, TRIV>), grid, block, 0, rs->stream, dev_ring<W>(rs), in, x0, dst1, d, n_d, nct, sm, sc, dup, bal);
+}
+
+// The digit tail of a two-power key-switch stage, `elems` coefficient elements at the transforms' ring rd, queued on ring `on`'s stream
+// (do_tunnel_pow2, do_hoisted).  BaseBGad 2^bw (bw > 0): x1 holds the elements ([elem][L][n_d]) and dig receives the crt of their GD
+// digits each -- decomposed and reduced in the transforms' loader (OP_CRT_BASE2) or, on split rings, by k_decompose_base2 + do_crt.
+// TrivGad (bw = 0): dig holds the digits already (k_tun2_gather wrote them decomposed and reduced) and takes one batched crt.
+template <typename W>
+static int pow2_digit_tail(alch_ring* rd, alch_ring* on, const char* x1, char* dig, size_t elems, u32 GD, u32 bw, const Scal<u32>& b2first,
+                           const Scal<u32>& b2kd) {
+    int rc;
+    if (bw > 0 && !split_ring(rd)) {
+        NttCall<W> nc{};
+        nc.op = OP_CRT_BASE2; nc.ring = &dev_ring<W>(rd); nc.stream = on->stream; nc.balanced = rd->balanced;
+        nc.src = reinterpret_cast<const W*>(x1); nc.data = reinterpret_cast<W*>(dig);
+        nc.npoly = elems * GD * (size_t)rd->L;
+        nc.b2_first = b2first; nc.b2_kd = b2kd; nc.b2_D = GD; nc.b2_w = bw;
+        return launch(rd, nc, "tunnel crt_base2");
+    }
+    if (bw > 0) {
+        for (size_t y0 = 0; y0 < elems; y0 += 32768) {             // grid.y is 16-bit
+            const unsigned ny = (unsigned)std::min<size_t>(32768, elems - y0);
+            launch_decompose_baseb<W>(rd, on->stream, dev_ring<W>(rd), ny, reinterpret_cast<const W*>(x1) + y0 * elem_words(rd),
+                                      reinterpret_cast<W*>(dig) + y0 * GD * elem_words(rd), b2first, b2kd, GD, bw);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    if ((rc = do_crt<W>(rd, dig, 0, elems * GD, false, nullptr, on)) != ALCH_OK) return rc;
+    return ALCH_OK;
 }
 
 // SymmSHE.tunnel between two two-power rings of the radix-16 engine (m >= 32 on both sides); same contract as do_tunnel.  Two shapes:
@@ -3916,25 +3952,7 @@ static int do_tunnel_pow2(const alch_tunnel* t, alch_ring* rin, const void* in, 
         // constant term: crt of the E'-coefficients of c0 (evalLin itself is the inner product's starting value)
         if (px0 && (rc = crt_suffix<W>(rd, dup, x0, now * d, false, rs)) != ALCH_OK) return rc;
         // linear term: the digits' crt
-        if (base2 && !split_ring(rd)) {                // decompose + reduce in the transforms' loader
-            NttCall<W> nc{};
-            nc.op = OP_CRT_BASE2; nc.ring = &dev_ring<W>(rd); nc.stream = rs->stream; nc.balanced = rd->balanced;
-            nc.src = reinterpret_cast<const W*>(x1); nc.data = reinterpret_cast<W*>(dig);
-            nc.npoly = now * (size_t)d * GD * (size_t)L;
-            nc.b2_first = b2first; nc.b2_kd = b2kd; nc.b2_D = GD; nc.b2_w = bw;
-            if ((rc = launch(rd, nc, "tunnel crt_base2")) != ALCH_OK) return rc;
-        } else {
-            if (base2) {
-                const size_t elems = now * d;
-                for (size_t y0 = 0; y0 < elems; y0 += 32768) {             // grid.y is 16-bit
-                    const unsigned ny = (unsigned)std::min<size_t>(32768, elems - y0);
-                    launch_decompose_baseb<W>(rd, rs->stream, dev_ring<W>(rd), ny, reinterpret_cast<const W*>(x1) + y0 * elem_words(rd),
-                                              reinterpret_cast<W*>(dig) + y0 * GD * elem_words(rd), b2first, b2kd, GD, bw);
-                    HIP_TRY(hipGetLastError());
-                }
-            }
-            if ((rc = do_crt<W>(rd, dig, 0, now * d * GD, false, nullptr, rs)) != ALCH_OK) return rc;
-        }
+        if ((rc = pow2_digit_tail<W>(rd, rs, x1, dig, now * d, GD, bw, b2first, b2kd)) != ALCH_OK) return rc;
         W* po = reinterpret_cast<W*>(reinterpret_cast<char*>(out) + done * 2 * ebs);
         const size_t pieces = (now + 3) / 4 * (size_t)L * (rs->n / Vec4<W>::LANES);
         const W* mx0 = c0_in_place ? reinterpret_cast<const W*>(src) : reinterpret_cast<const W*>(x0);
@@ -4122,6 +4140,188 @@ extern "C" int alch_ct_automorph(const void* handle, const alch_buf* in, alch_bu
         if (rc != ALCH_OK) return rc;
     }
     return ALCH_OK;
+} catch (...) { return abi_catch(); }
+
+// ------------------------------------------------------------------------------------------------------
+// Hoisted automorphisms (include/alchemy_hip.h, "Hoisted automorphisms"; kernel_hoist.hpp)
+// ------------------------------------------------------------------------------------------------------
+// Several sigma_j of one batch at one decomposition: the digits of s_pre c1 are brought to CRT form exactly as the ring-to-itself
+// tunnel's composed path brings them (do_tunnel_pow2 / do_tunnel with d_rel = 1, lin = crt(1); never the fused TrivGad kernels, which
+// keep no digits), then every rotation reads them through its slot permutation inside the hint inner product.
+struct alch_automorph_set {
+    alch_ring* ring;
+    int gadget, digits;                        // gadget code; D = its digit count on the ring
+    u32 n_j;
+    u32 j[HOIST_MAX];                          // reduced mod m
+    void* ks;                                  // the n_j hints one after the other, 2 D elements each, Montgomery form (owned)
+    u32* tabs;                                 // general engine: [n_j][n] slot tables (owned: the ring's cache may evict its own)
+    int32_t* ident;                            // general engine: the coefficient table of the tunnel from the ring to itself, k -> k
+};
+
+extern "C" int alch_automorph_set_free(void* handle) try {
+    alch_automorph_set* a = reinterpret_cast<alch_automorph_set*>(handle);
+    if (!a) return ALCH_OK;
+    (void)hipSetDevice(a->ring->device);
+    (void)hipStreamSynchronize(a->ring->stream);
+    if (a->ks) (void)hipFree(a->ks);
+    if (a->tabs) (void)hipFree(a->tabs);
+    if (a->ident) (void)hipFree(a->ident);
+    delete a;
+    return ALCH_OK;
+} catch (...) { return abi_catch(); }
+
+extern "C" int alch_automorph_set_create(alch_ring* ring, uint32_t n_j, const uint32_t* j, int gadget, const alch_buf* ks_crt, void** out) try {
+    if (!ring || !j || !ks_crt || !out) return fail(ALCH_E_INVALID, "alch_automorph_set_create: null argument");
+    *out = nullptr;
+    if (gadget_width(gadget) < 0) return fail(ALCH_E_INVALID, "alch_automorph_set_create: unknown gadget");
+    if (ks_crt->ring != ring) return fail(ALCH_E_INVALID, "alch_automorph_set_create: the hints live in the ring");
+    if (!ring->has_crt) return fail(ALCH_E_NO_CRT, "this ring has no CRT basis (created with alch_ring_create_nocrt)");
+    if (n_j < 1 || n_j > (uint32_t)HOIST_MAX)
+        return fail(ALCH_E_INVALID, "alch_automorph_set_create: a set holds 1 .. " + std::to_string(HOIST_MAX) + " units");
+    for (u32 r = 0; r < n_j; ++r)
+        if (automorph::gcd(j[r] % ring->m, ring->m) != 1)
+            return fail(ALCH_E_INVALID, "alch_automorph_set_create: j[" + std::to_string(r) + "] is not a unit mod m");
+    const int D = gadget_digits(ring, gadget);
+    const size_t nks = (size_t)n_j * 2 * (size_t)D;
+    if (ks_crt->n_elems < nks) return fail(ALCH_E_INVALID, "alch_automorph_set_create: need n_j * 2 * (gadget digits) hint elements");
+    BIND(ring);
+    alch_automorph_set* a = new alch_automorph_set{ring, gadget, D, n_j, {0}, nullptr, nullptr, nullptr};
+    for (u32 r = 0; r < n_j; ++r) a->j[r] = j[r] % ring->m;
+    if (hipMalloc(&a->ks, nks * elem_bytes(ring)) != hipSuccess) {
+        alch_automorph_set_free(a);
+        return fail(ALCH_E_NOMEM, "alch_automorph_set_create: hipMalloc(hints) failed");
+    }
+    if (ring->gen) {
+        automorph::Plan P;
+        if (automorph::plan(ring->m, P) != automorph::PLAN_OK || P.n != ring->n) {
+            alch_automorph_set_free(a);
+            return fail(ALCH_E_INTERNAL, "alch_automorph_set_create: the ring's index has no plan");
+        }
+        const size_t n = ring->n;
+        std::vector<uint32_t> all(n_j * n), t;
+        for (u32 r = 0; r < n_j; ++r) {
+            automorph::build_table(P, a->j[r], t);
+            std::copy(t.begin(), t.end(), all.begin() + r * n);
+        }
+        std::vector<int32_t> id(n);
+        for (size_t k = 0; k < n; ++k) id[k] = (int32_t)k;
+        if (hipMalloc((void**)&a->tabs, all.size() * sizeof(u32)) != hipSuccess || hipMalloc((void**)&a->ident, n * sizeof(int32_t)) != hipSuccess) {
+            alch_automorph_set_free(a);
+            return fail(ALCH_E_NOMEM, "alch_automorph_set_create: hipMalloc(tables) failed");
+        }
+        if (hipMemcpy(a->tabs, all.data(), all.size() * sizeof(u32), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(a->ident, id.data(), n * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+            alch_automorph_set_free(a);
+            return fail(ALCH_E_HIP, "alch_automorph_set_create: table upload failed");
+        }
+    }
+    int rc = ALCH_BY_WORD(ring, tunnel_to_mont, ring, a->ks, ks_crt->dptr, nks);
+    if (rc != ALCH_OK) { const std::string msg = g_err; alch_automorph_set_free(a); return fail(rc, msg); }
+    if (hipStreamSynchronize(ring->stream) != hipSuccess) { alch_automorph_set_free(a); return fail(ALCH_E_HIP, "alch_automorph_set_create: setup failed"); }
+    *out = a;
+    return ALCH_OK;
+} catch (...) { return abi_catch(); }
+
+// rotations r0 .. r0 + nrot - 1 of the set, accumulated into the `now` ciphertexts at po (kernel_hoist.hpp)
+template <typename W>
+static void launch_hoist_mac(alch_ring* r, W* po, const W* dig, const W* cin, size_t now, u32 D, const HoistSet<W>& S, u32 r0, u32 nrot,
+                             const Scal<W>& sm, bool scale) {
+    constexpr int VL = Vec4<W>::LANES;
+    const size_t tiles = (now + 3) / 4 * (size_t)r->L;
+    const int sc = scale ? 1 : 0;
+    if (!r->gen)                                   // n >= 16: a multiple of the vector width
+        hipLaunchKernelGGL((k_hoist_mac<W, VL, 4, true>), dim3(ew_grid(tiles * (r->n / VL))), dim3(256), 0, r->stream, dev_ring<W>(r), po, dig, cin, now, D, S,
+                           r0, nrot, r->logn, sm, sc);
+    else if (r->n % VL == 0)
+        hipLaunchKernelGGL((k_hoist_mac<W, VL, 4, false>), dim3(ew_grid(tiles * (r->n / VL))), dim3(256), 0, r->stream, dev_ring<W>(r), po, dig, cin, now, D, S,
+                           r0, nrot, 0, sm, sc);
+    else
+        hipLaunchKernelGGL((k_hoist_mac<W, 1, 4, false>), dim3(ew_grid(tiles * r->n)), dim3(256), 0, r->stream, dev_ring<W>(r), po, dig, cin, now, D, S,
+                           r0, nrot, 0, sm, sc);
+}
+
+template <typename W>
+static int do_hoisted(const alch_automorph_set* a, const void* in, void* out, size_t batch, const uint64_t* s_pre, bool sum) {
+    alch_ring* r = a->ring;
+    const int L = r->L;
+    const u32 bw = (u32)gadget_width(a->gadget);      // BaseBGad 2^bw; 0: TrivGad
+    const bool base2 = bw > 0;
+    const u32 GD = base2 ? (u32)a->digits : (u32)L;
+    Scal<u32> b2first, b2kd;
+    if (base2) base2_layout(r, b2first, b2kd, bw);
+    const size_t eb = elem_bytes(r), ew = elem_words(r);
+    // scratch per ciphertext: the Pow copy of the input (2 elements); the scaled c1 where a decomposition reads it (general engine:
+    // k_tunnel_gather writes the scaled c0 next to it); the GD digit elements
+    const size_t x0_b = r->gen ? eb : 0, x1_b = (r->gen || base2) ? eb : 0, dig_b = (size_t)GD * eb;
+    const size_t per_ct = 2 * eb + x0_b + x1_b + dig_b;
+    const size_t chunk = scratch_chunk(r->scratch_mib << 20, batch, per_ct);
+    int rc = r->ws_full.reserve(chunk * per_ct);
+    if (rc != ALCH_OK) return rc;
+    Carve cv(r->ws_full.p, chunk);
+    char *win = cv.take(2 * eb), *x0 = cv.take(x0_b), *x1 = cv.take(x1_b), *dig = cv.take(dig_b);
+    if (!cv.matches(per_ct)) return fail(ALCH_E_INTERNAL, "do_hoisted: the scratch carve differs from the bytes reserved per ciphertext");
+    uint64_t s_eff[MAXL] = {0};
+    for (int i = 0; i < L; ++i) s_eff[i] = up_scalar(r, 0, i, s_pre ? s_pre[i] : 1);
+    const bool scale = s_pre != nullptr;
+    Scal<W> sm;
+    scal_to_mont<W>(r, s_eff, 1, sm);
+    HoistSet<W> S{};
+    for (u32 t = 0; t < a->n_j; ++t) {
+        S.hint[t] = reinterpret_cast<const W*>(a->ks) + (size_t)t * 2 * GD * ew;
+        S.tab[t] = a->tabs ? a->tabs + (size_t)t * r->n : nullptr;
+        S.j[t] = a->j[t];
+    }
+    for (size_t done = 0; done < batch; done += chunk) {
+        const size_t now = std::min(chunk, batch - done);
+        const char* src = reinterpret_cast<const char*>(in) + done * 2 * eb;
+        if (!r->gen) {                                 // do_tunnel_pow2 with d = 1, up to its inner product
+            if ((rc = crt_into<W>(r, win, {src}, 2 * now, true, r)) != ALCH_OK) return rc;
+            const W* pow_in = reinterpret_cast<const W*>(win);
+            if (base2) launch_tun2_gather<W, false>(r, 1, pow_in, nullptr, reinterpret_cast<W*>(x1), r->n, now, sm, scale, 0u);
+            else launch_tun2_gather<W, true>(r, 1, pow_in, nullptr, reinterpret_cast<W*>(dig), r->n, now, sm, scale, 0u);
+            HIP_TRY(hipGetLastError());
+            if ((rc = pow2_digit_tail<W>(r, r, x1, dig, now, GD, bw, b2first, b2kd)) != ALCH_OK) return rc;
+        } else {                                       // do_tunnel with d_rel = 1, rx = the ring, up to its inner product
+            if ((rc = do_crt<W>(r, win, 0, 2 * now, true, src, r)) != ALCH_OK) return rc;
+            const size_t gw = now * 2 * ew;
+            ALCH_LAUNCH_VW(k_tunnel_gather, r, gw, r->stream, dev_ring<W>(r), (const W*)win, (const W*)win, (W*)x0, (W*)x1, a->ident, 1u, r->n, now, sm,
+                           scale ? 1 : 0, (u32)L, 0u, 0u);
+            HIP_TRY(hipGetLastError());
+            if ((rc = gen_digit_tail<W>(r, r, x1, dig, now, GD, (u32)L, 0u, bw, b2first, b2kd)) != ALCH_OK) return rc;
+        }
+        const W* cin = reinterpret_cast<const W*>(src);
+        const W* pd = reinterpret_cast<const W*>(dig);
+        if (sum) {
+            launch_hoist_mac<W>(r, reinterpret_cast<W*>(reinterpret_cast<char*>(out) + done * 2 * eb), pd, cin, now, GD, S, 0u, a->n_j, sm, scale);
+            HIP_TRY(hipGetLastError());
+        } else {
+            for (u32 t = 0; t < a->n_j; ++t) {
+                launch_hoist_mac<W>(r, reinterpret_cast<W*>(reinterpret_cast<char*>(out) + ((size_t)t * batch + done) * 2 * eb), pd, cin, now, GD, S, t, 1u,
+                                    sm, scale);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+    }
+    return ALCH_OK;
+}
+
+extern "C" int alch_ct_automorph_hoisted(const void* handle, const alch_buf* in, alch_buf* out, size_t batch, const uint64_t* s_pre, unsigned flags) try {
+    const alch_automorph_set* a = reinterpret_cast<const alch_automorph_set*>(handle);
+    if (!a || !in || !out) return fail(ALCH_E_INVALID, "alch_ct_automorph_hoisted: null argument");
+    alch_ring* r = a->ring;
+    if (in->ring != r || out->ring != r) return fail(ALCH_E_INVALID, "alch_ct_automorph_hoisted: input and output buffers belong to the set's ring");
+    if (flags & ~(unsigned)(ALCH_POW_IN | ALCH_POW_OUT | ALCH_AUTO_SUM)) return fail(ALCH_E_INVALID, "alch_ct_automorph_hoisted: unknown flag");
+    if (flags & (ALCH_POW_IN | ALCH_POW_OUT))
+        return fail(ALCH_E_UNSUPPORTED, "alch_ct_automorph_hoisted: CRT basis in and out only (on the powerful basis sigma_j is not a permutation: transform first)");
+    if (batch == 0) return ALCH_OK;
+    const bool sum = (flags & ALCH_AUTO_SUM) != 0;
+    const size_t rots = sum ? 1 : (size_t)a->n_j;
+    if (!pairs_ok(batch, in->n_elems) || batch > out->n_elems / 2 / rots)
+        return fail(ALCH_E_INVALID, "alch_ct_automorph_hoisted: in holds 2 * batch elements, out 2 * n_j * batch (2 * batch with ALCH_AUTO_SUM)");
+    const size_t eb = elem_bytes(r);
+    if (bytes_overlap(out->dptr, 2 * rots * batch * eb, in->dptr, 2 * batch * eb)) return fail(ALCH_E_INVALID, "alch_ct_automorph_hoisted: out must not alias the input");
+    BIND(r);
+    return ALCH_BY_WORD(r, do_hoisted, a, in->dptr, out->dptr, batch, s_pre, sum);
 } catch (...) { return abi_catch(); }
 
 // ------------------------------------------------------------------------------------------------------

@@ -19,6 +19,14 @@
 #else
 #define ALCH_AUTO_HD
 #endif
+#if defined(__has_builtin)
+#if __has_builtin(__builtin_bitreverse32)
+#define ALCH_AUTO_HAS_BITREVERSE 1        // clang on the host as well: the sweep of tests/sanitize/hoist_harness.cpp evaluates it 10^10 times
+#endif
+#endif
+#ifndef ALCH_AUTO_HAS_BITREVERSE
+#define ALCH_AUTO_HAS_BITREVERSE 0
+#endif
 
 namespace alch {
 namespace automorph {
@@ -100,7 +108,7 @@ inline bool build_table(const Plan& P, uint32_t j, std::vector<uint32_t>& out) {
 
 // The low `bits` bits of x reversed (bits <= 32; 0 gives 0).
 ALCH_AUTO_HD inline uint32_t brev_bits(uint32_t x, int bits) {
-#if defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__) || ALCH_AUTO_HAS_BITREVERSE
     return bits ? __builtin_bitreverse32(x) >> (32 - bits) : 0u;      // what __brev is: v_bfrev_b32, without the HIP runtime header
 #else
     uint32_t r = 0;
@@ -116,6 +124,21 @@ ALCH_AUTO_HD inline uint32_t pow2_src(uint32_t k, uint32_t j, int logn) {
     const uint32_t u = 2u * brev_bits(k, logn) + 1u;
     const uint32_t v = (u * j) & ((2u << logn) - 1u);
     return brev_bits(v >> 1, logn);
+}
+
+// The aligned pack of VL destination slots that starts at k0 (VL a power of two, VL | k0, VL <= n): the slots share the low bits of
+// brev(k), so their units agree mod 2n / VL and so do the products with j -- all VL source slots lie in ONE aligned pack of VL.
+// Returns the first slot of that pack; pick[c] is where in it destination slot k0 + c reads.  The hoisted inner product
+// (kernel_hoist.hpp) computes this once per item and reuses it for c0, every digit and every ciphertext of its tile.
+template <int VL>
+ALCH_AUTO_HD inline uint32_t pow2_pack(uint32_t k0, uint32_t j, int logn, uint32_t (&pick)[VL]) {
+    const uint32_t s0 = pow2_src(k0, j, logn);
+    pick[0] = s0 & (uint32_t)(VL - 1);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int c = 1; c < VL; ++c) pick[c] = pow2_src(k0 + (uint32_t)c, j, logn) & (uint32_t)(VL - 1);
+    return s0 & ~(uint32_t)(VL - 1);
 }
 
 }  // namespace automorph

@@ -173,3 +173,8 @@ foreign import ccall safe   "alch_buf_automorph"       c_bufAutomorph    :: Ptr 
 foreign import ccall safe   "alch_automorph_create"    c_automorphCreate :: Ptr AlchRing -> Word32 -> CInt -> Ptr AlchBuf -> Ptr (Ptr ()) -> IO CInt
 foreign import ccall safe   "alch_automorph_free"      c_automorphFree   :: Ptr () -> IO CInt
 foreign import ccall safe   "alch_ct_automorph"        c_ctAutomorph     :: Ptr () -> Ptr AlchBuf -> Ptr AlchBuf -> CSize -> Ptr Word64 -> CUInt -> IO CInt
+-- Hoisted automorphisms (include/alchemy_hip.h, "Hoisted automorphisms"): several sigma_j of one batch at one gadget decomposition.  The
+-- set's handle is untyped like alch_automorph's; create and the call take the device lock and may wait, free waits for the stream
+foreign import ccall safe   "alch_automorph_set_create" c_automorphSetCreate :: Ptr AlchRing -> Word32 -> Ptr Word32 -> CInt -> Ptr AlchBuf -> Ptr (Ptr ()) -> IO CInt
+foreign import ccall safe   "alch_automorph_set_free"  c_automorphSetFree :: Ptr () -> IO CInt
+foreign import ccall safe   "alch_ct_automorph_hoisted" c_ctAutomorphHoisted :: Ptr () -> Ptr AlchBuf -> Ptr AlchBuf -> CSize -> Ptr Word64 -> CUInt -> IO CInt

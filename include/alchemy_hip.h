@@ -75,6 +75,7 @@ typedef struct alch_tunnel alch_tunnel;
 /* flags of alch_ct_mul_relin */
 #define ALCH_POW_IN 1u             /* inputs are in the Pow basis (crt applied first)          */
 #define ALCH_POW_OUT 2u            /* outputs wanted in the Pow basis (crtInv applied last)     */
+#define ALCH_AUTO_SUM 4u           /* alch_ct_automorph_hoisted: one output batch, the sum over the set's rotations */
 
 /* gadgets (Crypto/Alchemy/Interpreter/PT2CT.hs:139-140) */
 #define ALCH_GAD_TRIV 0            /* TrivGad: one digit per limb, centred lift                 */
@@ -254,7 +255,7 @@ int alch_buf_view(const alch_buf *parent, size_t first, size_t count, alch_buf *
  * Entry points between two rings whose limb counts differ (alch_ct_mod_switch(_deg), alch_buf_rescale_drop0 / _add0) cannot be
  * given overlapping ranges: a view keeps its parent's ring.  Those that accept one ring on both sides (alch_buf_embed / _twace /
  * _coeffs with equal indices, alch_ct_tunnel from a ring to itself, alch_ct_mul_full with operands and result on one ring,
- * alch_buf_automorph, alch_ct_automorph) follow the rule without exception. */
+ * alch_buf_automorph, alch_ct_automorph, alch_ct_automorph_hoisted) follow the rule without exception. */
 int alch_buf_elems(const alch_buf *buf, size_t *n_elems);
 /* Device address and size of the buffer (limb-major words, see above) for zero-copy hand-off to other device
  * code on the same GPU -- RCCL collectives that gather result batches, a caller's own kernels.
@@ -507,6 +508,35 @@ int alch_buf_automorph(alch_buf *dst, size_t dst_first, const alch_buf *src, siz
 int alch_automorph_create(alch_ring *ring, uint32_t j, int gadget, const alch_buf *ks_crt, void **out);
 int alch_automorph_free(void *a);
 int alch_ct_automorph(const void *a, const alch_buf *in, alch_buf *out, size_t batch, const uint64_t *s_pre, unsigned flags);
+
+/* ---- Hoisted automorphisms (added within 1.8; probe for the symbols) ---------------------------------------------------------------
+ * Several sigma_j of the SAME ciphertexts at ONE gadget decomposition.  Almost all of alch_ct_automorph's key switch is the
+ * decomposition of c1 and the forward transforms of its D digits; sigma_j fixes Z_q, the gadget entries g_t are constants of Z_q, so
+ * with s_pre c1 = sum_t g_t d_t also sigma_j(s_pre c1) = sum_t g_t sigma_j(d_t), the sigma_j(d_t) as short as the d_t.  On the CRT
+ * basis sigma_j is the slot permutation src_j (alch_automorph_table), hence
+ *       out_j.c0[k] = s_pre c0[src_j[k]] + sum_t crt(d_t)[src_j[k]] b_{j,t}[k]
+ *       out_j.c1[k] =                      sum_t crt(d_t)[src_j[k]] a_{j,t}[k]
+ * is a key switch of sigma_j(ct) under the hint alch_automorph_create takes for j: one decomposition and D transforms for all the
+ * rotations, one gathered inner product per rotation.  WORD FOR WORD, with j' the inverse of j mod m and h' = alch_buf_automorph by j'
+ * of the hint, out_j = alch_buf_automorph_j(alch_ct_tunnel(identity tunnel from crt(1) and h')(ct, s_pre)).  It equals
+ * alch_ct_automorph's words for j = 1, and for TrivGad on two-power rings; elsewhere the digits differ (decompose-then-permute against
+ * permute-then-decompose), both are valid key switches with the same noise bound.
+ *   alch_automorph_set_create   n_j units (1 <= n_j <= 32; each reduced mod m, repeats allowed), one gadget; ks_crt holds the n_j
+ *           hints one after the other, 2 * D elements each in the layout and meaning of alch_automorph_create.  Copied (Montgomery
+ *           form) at create time.  The handle is the library's `alch_automorph_set`, an untyped `void *` like alch_automorph's.
+ *           Statuses, in this order: ALCH_E_INVALID (null argument; unknown gadget; the hint on another ring), ALCH_E_NO_CRT,
+ *           ALCH_E_INVALID (n_j outside 1..32; a j that is no unit; fewer than n_j * 2 * D hint elements), device errors last.
+ *   alch_ct_automorph_hoisted   linear ciphertexts with k = 0, CRT basis in and out, `in` (batch ciphertexts) and `out` on the set's
+ *           ring.  out holds n_j * batch ciphertexts: rotation r of ciphertext b at elements 2 (r batch + b) and 2 (r batch + b) + 1.
+ *           ALCH_AUTO_SUM: out holds batch ciphertexts, sum_r out_(j_r)[b] (rotate-and-sum, traces), from one launch per chunk.
+ *           s_pre = toMSD's per-limb scalar (NULL = 1).  Runs on the ring's stream in chunks of at most "scratch_mib"; the input is
+ *           not modified; out shares no byte with in.  batch = 0: ALCH_OK, nothing queued.
+ *           Statuses, in this order: ALCH_E_INVALID (null argument; buffers of another ring; an unknown flag), ALCH_E_UNSUPPORTED
+ *           (ALCH_POW_IN / ALCH_POW_OUT), ALCH_E_INVALID (a buffer shorter than its ciphertexts; out overlapping in), device errors.
+ * Free the set with alch_automorph_set_free when no call is using it. */
+int alch_automorph_set_create(alch_ring *ring, uint32_t n_j, const uint32_t *j, int gadget, const alch_buf *ks_crt, void **out);
+int alch_automorph_set_free(void *set);
+int alch_ct_automorph_hoisted(const void *set, const alch_buf *in, alch_buf *out, size_t batch, const uint64_t *s_pre, unsigned flags);
 
 /* ---- SymmSHE modSwitch on batches of linear ciphertexts (Eval.hs:130; the two modSwitch_ of PT2CT.hs:177 and :224-229) ----
  * The rings come from the handles; the smaller ring's moduli are the LAST limbs of the bigger ring's (Noise.hs:82-89).  The
