@@ -163,7 +163,7 @@ __device__ __forceinline__ void buf_st16(Rsrc r, u32 voff, u32 soff, u32 __attri
 // and q_added * x into the others (a scalar, folded into spre by the host), so an added limb j < dup starts
 // from c0 = c1 = 0, has a zero diagonal digit and transforms all L - dup digits; hint row of source digit i is
 // i + dup (the digits of the added limbs are zero and are skipped).
-// Q30 (every modulus below 2^30, so 4q fits a word): Harvey's forward butterflies (8 instructions instead of 10, values lazy in [0,4q)
+// Q30 (every modulus below 2^30, so 4q fits a word): Harvey's forward butterflies (7 instructions instead of 9, values lazy in [0,4q)
 // through pass G and the LDS passes -- the hint product takes any word), accumulators lazy in [0,2q) (one conditional subtraction per
 // product instead of two) and brought to [0,q) when they are stored.
 template <int LOGN, bool BALANCED, int EPT = 32, bool UP = false, bool Q30 = false>

@@ -71,8 +71,25 @@ ALCH_HD W add_mod(W a, W b, W q) { return csub((W)(a + b), q); }            // a
 template <typename W>
 ALCH_HD W sub_mod(W a, W b, W q) { W d = a - b; W e = d + q; return e < d ? e : d; }   // a,b in [0,q)
 
+// The difference leg of a forward butterfly, xx + (c - t) with t <= c (c = q after a csub, c = 2q for Harvey's form where t < 2q):
+// c - t = |c - t|, so the leg is an absolute difference plus xx -- the same word, not merely a congruent one -- and gfx950 has that
+// as ONE instruction, v_sad_u32 D = |A - B| + C (A = c stays in its scalar register), where the plain form compiles to a subtract
+// and an add.  hipcc forms it from the expression below; the host compiles the same line.
+// ALCH_BFLY_SAD = 0: the subtract-and-add form (A/B builds, tools/build_variant.sh).
+#ifndef ALCH_BFLY_SAD
+#define ALCH_BFLY_SAD 1
+#endif
+ALCH_HD u32 diff_leg(u32 xx, u32 c, u32 t) {
+#if ALCH_BFLY_SAD
+    return (c > t ? c - t : t - c) + xx;
+#else
+    return xx + (c - t);
+#endif
+}
+
 // Forward (Cooley-Tukey) butterfly on lazy values: x,y in [0,2q), w = twiddle in Montgomery form.
-//   x' = x + w*y, y' = x - w*y   (mod q), outputs in [0,2q).  10 VALU instructions for W = u32.
+//   x' = x + w*y, y' = x - w*y   (mod q), outputs in [0,2q).  W = u32: 9 VALU instructions (three multiplier instructions, two
+// conditional subtractions of two each, one add, one v_sad_u32); W = u64 keeps the subtract-and-add leg.
 template <typename W>
 ALCH_HD void bfly_fwd(W& x, W& y, W w, W q, W qni) {
     W xx = csub(x, q);
@@ -80,15 +97,22 @@ ALCH_HD void bfly_fwd(W& x, W& y, W w, W q, W qni) {
     x = xx + t;
     y = xx + (q - t);
 }
+ALCH_HD void bfly_fwd(u32& x, u32& y, u32 w, u32 q, u32 qni) {
+    const u32 xx = csub(x, q);
+    const u32 t = csub(mont_mul_lazy(y, w, q, qni), q);
+    x = xx + t;
+    y = diff_leg(xx, q, t);
+}
 
 // q < 2^30 (4q fits a word): Harvey's lazy butterflies.  Forward: x, y in [0,4q) -> [0,4q); the product takes ANY word, so y is
-// never reduced.  8 VALU instructions instead of 10.  Inverse: x, y in [0,2q) -> [0,2q); 8 instead of 10.
+// never reduced.  7 VALU instructions instead of 9 (the difference leg is |2q - t| + xx, t < 2q).  Inverse: x, y in [0,2q) -> [0,2q);
+// 8 instead of 10.
 ALCH_HD void bfly_fwd4(u32& x, u32& y, u32 w, u32 q, u32 qni) {
     const u32 q2 = 2u * q;
     const u32 xx = csub(x, q2);
     const u32 t = mont_mul_lazy(y, w, q, qni);
     x = xx + t;
-    y = xx + (q2 - t);
+    y = diff_leg(xx, q2, t);
 }
 ALCH_HD void bfly_inv4(u32& x, u32& y, u32 w, u32 q, u32 qni) {
     const u32 q2 = 2u * q;

@@ -11,6 +11,7 @@ constexpr int UNROLL = 16;
 
 enum Op { ADD_VV, ADD_VS, MIN_VV, MIN_VS, MAX_VS, MINI_VS, CMP_CND, SUBCO_CND, ADD3, LSHLADD, AND_VS, ASHR, MED3,
           DPP_ROR8, DPP_QP, DPP_MIRROR, PERMLANE32, SWIZZLE, BPERMUTE, MOV, BF_STRICT_MIN, BF_STRICT_CND, BF_X1Q, BF_LAZY30,
+          SAD_SVV, ADD_SUB_PAIR, BF_SAD,
           LDS_R32, LDS_W32, LDS_R128, LDS_W128, NOPS };
 
 template <int OP>
@@ -49,6 +50,10 @@ __global__ void __launch_bounds__(256) k_rate(uint32_t* out, uint32_t seed, uint
             else if constexpr (OP == AND_VS) { asm volatile("v_and_b32 %0, %1, %0" : "+v"(x[i]) : "s"(q)); }
             else if constexpr (OP == ASHR) { asm volatile("v_ashrrev_i32 %0, 3, %0" : "+v"(x[i])); }
             else if constexpr (OP == MED3) { asm volatile("v_med3_u32 %0, %0, %1, %2" : "+v"(x[i]) : "v"(w), "s"(q)); }
+            else if constexpr (OP == SAD_SVV) { asm volatile("v_sad_u32 %0, %1, %0, %2" : "+v"(x[i]) : "s"(q), "v"(w)); }      // |q - x| + w
+            else if constexpr (OP == ADD_SUB_PAIR) {          // the dependent pair v_sad_u32 replaces in the butterfly; one unit = both
+                asm volatile("v_add_u32 %0, %1, %0\n\tv_sub_u32 %0, %0, %2" : "+v"(x[i]) : "s"(q), "v"(w));
+            }
             else if constexpr (OP == MOV) { asm volatile("v_mov_b32 %0, %1" : "=v"(x[i]) : "v"(y[i])); }
             else if constexpr (OP == DPP_ROR8) { asm volatile("v_mov_b32_dpp %0, %1 row_ror:8 row_mask:0xf bank_mask:0xf" : "=v"(x[i]) : "v"(y[i])); }
             else if constexpr (OP == DPP_QP) { asm volatile("v_add_u32_dpp %0, %1, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "+v"(x[i]) : "v"(y[i])); }
@@ -91,6 +96,15 @@ __global__ void __launch_bounds__(256) k_rate(uint32_t* out, uint32_t seed, uint
                 t = min(t, t - q);
                 uint32_t xx = min(x[i], x[i] - q);
                 x[i] = xx + t; y[i] = xx + (q - t);
+            }
+            else if constexpr (OP == BF_SAD) {
+                // bf x<q lazy with the difference leg as |q - t| + xx (t < q after its csub: the same word): 9 instructions
+                unsigned long long p = (unsigned long long)y[i] * w;
+                uint32_t m = (uint32_t)p * qinv;
+                uint32_t t = (uint32_t)((p + (unsigned long long)m * q) >> 32);
+                t = min(t, t - q);
+                uint32_t xx = min(x[i], x[i] - q);
+                x[i] = xx + t; y[i] = (q > t ? q - t : t - q) + xx;
             }
             else if constexpr (OP == BF_LAZY30) {
                 unsigned long long p = (unsigned long long)y[i] * w;
@@ -172,6 +186,9 @@ int main() {
         run<BF_STRICT_CND>("bf strict cnd", w);
         run<BF_X1Q>("bf x<q lazy", w);
         run<BF_LAZY30>("bf lazy30", w);
+        run<SAD_SVV>("sad_u32 s,v,v", w);
+        run<ADD_SUB_PAIR>("add v,s+sub vv", w);
+        run<BF_SAD>("bf sad", w);
     }
     return 0;
 }
