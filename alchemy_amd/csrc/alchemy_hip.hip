@@ -79,7 +79,7 @@ struct alch_ring {
     std::shared_ptr<StreamOwner> stream_owner;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     void* tables = nullptr;                    // all twiddle tables, one allocation
-    void* tables_p = nullptr;                  // Plantard forward constants (32-bit rings) / Shoup pairs (64-bit rings)
+    void* tables_p = nullptr;                  // Plantard forward and inverse constants (32-bit rings) / Shoup pairs (64-bit rings)
     DevRing<u32> d32;
     DevRing<u64> d64;
     Scratch ws_digits;                         // digit scratch, two halves of [chunk][L][n] signed words
@@ -1369,19 +1369,26 @@ static int build_dev_ring(alch_ring* r, DevRing<W>& d) {
     }
     HIP_TRY(hipMemcpy(r->tables, all.data(), all.size() * sizeof(W), hipMemcpyHostToDevice));
     if (sizeof(W) == 4) {
-        // forward twiddles once more as Plantard constants: tw[k] = psi^brev(k)
-        std::vector<u64> pl((size_t)L * n);
+        // forward and inverse twiddles once more as Plantard constants: tw[k] = psi^brev(k), twi[k] = psi^-brev(k) (plain residues)
+        std::vector<u64> pl(2 * (size_t)L * n);
         for (int j = 0; j < L; ++j) {
             const u64 q = r->q[j];
-            const u64 psi = h_root(q, r->m);
-            std::vector<u64> pw(n);
-            u64 acc = 1;
-            for (size_t i = 0; i < n; ++i) { pw[i] = acc; acc = h_mulmod(acc, psi, q); }
-            for (size_t k = 0; k < n; ++k) pl[(size_t)j * n + k] = h_plant_const(pw[h_brev((u32)k, r->logn)], q);
+            const u64 psi = h_root(q, r->m), ipsi = h_powmod(psi, q - 2, q);
+            std::vector<u64> pw(n), ipw(n);
+            u64 acc = 1, iacc = 1;
+            for (size_t i = 0; i < n; ++i) { pw[i] = acc; ipw[i] = iacc; acc = h_mulmod(acc, psi, q); iacc = h_mulmod(iacc, ipsi, q); }
+            for (size_t k = 0; k < n; ++k) {
+                const u32 e = h_brev((u32)k, r->logn);
+                pl[(size_t)(2 * j) * n + k] = h_plant_const(pw[e], q);
+                pl[(size_t)(2 * j + 1) * n + k] = h_plant_const(ipw[e], q);
+            }
         }
         HIP_TRY(hipMalloc(&r->tables_p, pl.size() * sizeof(u64)));
         HIP_TRY(hipMemcpy(r->tables_p, pl.data(), pl.size() * sizeof(u64), hipMemcpyHostToDevice));
-        for (int j = 0; j < L; ++j) d.twp[j] = reinterpret_cast<const u64*>(r->tables_p) + (size_t)j * n;
+        for (int j = 0; j < L; ++j) {
+            d.twp[j] = reinterpret_cast<const u64*>(r->tables_p) + (size_t)(2 * j) * n;
+            d.twpi[j] = reinterpret_cast<const u64*>(r->tables_p) + (size_t)(2 * j + 1) * n;
+        }
     } else {
         // 64-bit rings: the transforms multiply by Shoup pairs (plain twiddle, floor(w 2^64 / q)); the Montgomery
         // tables above still serve the hand-written stage 0 of the split kernels
@@ -2753,7 +2760,7 @@ static DevRing<W> suffix_view(const alch_ring* r, int u) {
     d.L = r->L - u;
     for (int j = 0; j + u < r->L; ++j) {
         d.mod[j] = d.mod[j + u]; d.ninv_m[j] = d.ninv_m[j + u]; d.w1ninv_m[j] = d.w1ninv_m[j + u];
-        d.twf[j] = d.twf[j + u]; d.twi[j] = d.twi[j + u]; d.twp[j] = d.twp[j + u];
+        d.twf[j] = d.twf[j + u]; d.twi[j] = d.twi[j + u]; d.twp[j] = d.twp[j + u]; d.twpi[j] = d.twpi[j + u];
         d.tws[j] = d.tws[j + u]; d.twsi[j] = d.twsi[j + u];
     }
     return d;

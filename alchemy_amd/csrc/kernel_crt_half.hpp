@@ -59,7 +59,7 @@ k_crt_half(DevRing<W> R, W* __restrict__ data, const W* __restrict__ src, size_t
                 *reinterpret_cast<V*>(&lds[swz<LOGM>(idx)]) = u0;
             }
         }
-        const auto tw = fwd_tw(R, j);
+        const auto tw = fwd_tw_shared(R, j);
         const auto twm = fwd_twm(R, j);
 #pragma unroll 1
         for (int half = 0; half < 2; ++half) {
@@ -75,7 +75,7 @@ k_crt_half(DevRing<W> R, W* __restrict__ data, const W* __restrict__ src, size_t
             lds_barrier();
             ntt_pass<LOGM, LT, W, F, 4, false, false, false>(lds, tw, q, qni, (W)0, (W)0, tid, prefix, none);
             lds_barrier();
-            ntt_pass<LOGM, LT, W, F + 4, 4, false, false, false>(lds, tw, q, qni, (W)0, (W)0, tid, prefix, none);
+            ntt_pass<LOGM, LT, W, F + 4, 4, false, false, false>(lds, fwd_pass_tw<4, T>(tw, twm), q, qni, (W)0, (W)0, tid, prefix, none);
             pair_sync<LOGM>();
             ntt_pass<LOGM, LT, W, F + 8, 4, false, false, false>(lds, twm, q, qni, (W)0, (W)0, tid, prefix, none);
             lds_barrier();

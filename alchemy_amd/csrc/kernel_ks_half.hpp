@@ -31,7 +31,12 @@
 // limb i + dup of the hint's ring.  Both bring the coefficient to [0, q_i) and store  v > (q_i - 1)/2 ? v - q_i : v  (k_tensor_intt:
 // the `epi` lambda of its last inverse pass, kernels_ntt.hpp "W v = csub(x[k], q); SW z = v > half ? ..."; k_tensor_intt_split: the
 // "centred lift, digit stores" loop of kernel_tensor_split.hpp, z0 / z1 from c0, c1 < q);  every q_i of a 32-bit ring is below 2^31.  The composed key switch (ks_stage, with or without a ready c2) feeds k_hint_mac*, never this kernel.
-// ALCH_USE_PLANTARD builds keep the previous pass G (their shared twiddles are not Montgomery words); so does -DALCH_KS_SIGNED01=0.
+// Its two table words are Montgomery words read from R.twf whatever table stage 2 and the LDS passes use.  -DALCH_KS_SIGNED01=0 keeps
+// the previous pass G.
+// Twiddle tables (!Q30).  Stage 2 of pass G and the LDS pass with wave-uniform twiddles (LB >= 6, n = 2^15) read Plantard constants
+// (ALCH_PLANT3_FWD, ntt_engine.hpp): the 7-instruction butterfly, whose outputs are below 2q -- what the next Plantard or
+// Montgomery pass and the hint product take.  The LB = 4 pass has its own switch (ALCH_PLANT3_FWD_LB4), the per-lane last pass keeps
+// Montgomery words.  Q30 instantiations read the Montgomery table everywhere (bfly_fwd4).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -54,11 +59,11 @@
 #define ALCH_A_PARTIALS 0
 #endif
 // 1: stages 0-1 of pass G as one signed sum over the centred digits (stage01_signed, modarith.hpp); 0: the lazy stage 0 and two
-// butterflies it replaced.  Plantard builds keep the old form (their twiddles are not Montgomery words).
+// butterflies it replaced.
 #ifndef ALCH_KS_SIGNED01
 #define ALCH_KS_SIGNED01 1
 #endif
-#define KS_SIGNED01 (ALCH_KS_SIGNED01 && !ALCH_USE_PLANTARD)
+#define KS_SIGNED01 ALCH_KS_SIGNED01
 // Ablation switches (ALCH_EXP_FLAGS; wrong results, timing only) exist in -DALCH_ABLATE builds alone: in the product
 // kernel they cost real instructions (the compiler hoists e.g. the "skip the tensor part" zero-fill in front of the branch).
 #ifdef ALCH_ABLATE
@@ -124,10 +129,6 @@ namespace alch {
 #define KS_STAMP_INIT() do {} while (0)
 #define KS_STAMP_FLUSH() do {} while (0)
 #endif
-
-// y * twiddle, fully reduced, for either twiddle representation
-__device__ __forceinline__ u32 tw_mul(u32 y, u64 br, u32 q, u32) { return plant_mul(y, br, q); }
-__device__ __forceinline__ u32 tw_mul(u32 y, u32 w, u32 q, u32 qni) { return csub(mont_mul_lazy(y, w, q, qni), q); }
 
 // Global memory goes through buffer instructions: one descriptor per array (wave-uniform, from the kernel arguments),
 // the per-lane part of every address is the single VGPR `lane16` = threadIdx.x * 16 bytes, everything else (work
@@ -353,10 +354,11 @@ k_ks_accum_half(DevRing<u32> R, const u32* __restrict__ a, const u32* __restrict
         const u32 d = ((KS_DBG(2u) ? (u32)(ct & 7) : (u32)ct) * (u32)Ls + (u32)i) * ROW;   // byte offset of digit i
         // Nothing below depends on i except d and the hint rows; keep addresses and twiddles from being
         // hoisted out of the digit loop (that costs ~250 spilled VGPRs).
-        auto twf = fwd_tw(R, j);                        // Plantard constants (shared-twiddle passes)
+        auto twf = pick_tw<!Q30>(fwd_tw_shared(R, j), R.twf[j]);   // stage 2 and the wave-uniform pass: Plantard constants unless Q30
         const W* twm = R.twf[j];                        // Montgomery words (per-lane last pass)
         int tid = threadIdx.x;
         asm volatile("" : "+s"(twf), "+s"(twm), "+v"(tid));
+        auto tw4 = pick_tw<ALCH_PLANT3_FWD && ALCH_PLANT3_FWD_LB4 && !Q30>(twf, twm);     // the LB = 4 pass
 #if KS_SIGNED01
         asm volatile("" : "+s"(tw1), "+s"(tw2));
         // Constants of stage01_signed for this item (limb j, half hf), centred; negated where the negated digit is transformed (!Q30).
@@ -378,13 +380,9 @@ k_ks_accum_half(DevRing<u32> R, const u32* __restrict__ a, const u32* __restrict
             // !Q30: the NEGATED digit is transformed (the hint step subtracts its products, see sub_lazy): with
             // xh = -x, yh = -y in [0,2q) stage 0 is  xh - w1' yh,  w1' = -w1 (lower half: -(x + w1 y)) or w1 (upper).
             constexpr bool NEG = !Q30;                         // this instantiation transforms the negated digit
-#if ALCH_USE_PLANTARD
-            const auto w1 = twf[1];
-#else
-            const W w1 = ((hf != 0) != NEG) ? q - twf[1] : twf[1];     // -w1 for the upper half, or for the lower half when negated
-#endif
+            const W w1 = ((hf != 0) != NEG) ? q - twm[1] : twm[1];     // -w1 for the upper half, or for the lower half when negated
             const W nr1 = q - m.r1;                            // -1 in Montgomery form (unbalanced reduce of a negated digit)
-            const auto w2 = twf[2 + hf];
+            const W w2 = twm[2 + hf];
 #endif
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
@@ -430,15 +428,9 @@ k_ks_accum_half(DevRing<u32> R, const u32* __restrict__ a, const u32* __restrict
                             xx = csub(mont_mul_lazy((W)((W)zx[e] + R.dig_off[j]), m.r1, q, qni), q);
                             yr = mont_mul_lazy((W)((W)zy[e] + R.dig_off[j]), m.r1, q, qni);
                         }
-#if ALCH_USE_PLANTARD
-                        if constexpr (NEG) xx = csub(xx, q);
-                        const W t = tw_mul(yr, w1, q, qni);
-                        u[k][e] = hf ? xx + (q - t) : xx + t;
-#else
                         const W t = mont_mul_lazy(yr, w1, q, qni);                                      // [0, 2q)
                         if constexpr (NEG) u[k][e] = sub_lazy(xx, t, 2u * q);                           // [0, 2q)
                         else u[k][e] = xx + t;                                                          // Q30: below 3q
-#endif
                     }
                 }
 #pragma unroll
@@ -486,10 +478,11 @@ k_ks_accum_half(DevRing<u32> R, const u32* __restrict__ a, const u32* __restrict
         constexpr int NP = (LOGM - 2) / 4;
         typedef typename std::remove_cv<typename std::remove_pointer<decltype(twf)>::type>::type TWF;
         typedef typename std::remove_cv<typename std::remove_pointer<decltype(twm)>::type>::type TWM;
+        typedef typename std::remove_cv<typename std::remove_pointer<decltype(tw4)>::type>::type TW4;
         if constexpr (NP == 1) {
             ntt_pass<LOGM, LT, W, 2, 4, false, false, true, TWM, NoEpilogue&, true, Q30>(lds, twm, q, qni, (W)0, (W)0, tid, prefix, none);
         } else if constexpr (NP == 2) {
-            ntt_pass<LOGM, LT, W, 2, 4, false, false, ALCH_KS_SERIAL, TWF, NoEpilogue&, true, Q30>(lds, twf, q, qni, (W)0, (W)0, tid, prefix, none);
+            ntt_pass<LOGM, LT, W, 2, 4, false, false, ALCH_KS_SERIAL, TW4, NoEpilogue&, true, Q30>(lds, tw4, q, qni, (W)0, (W)0, tid, prefix, none);
             pair_sync<LOGM>();                    // LB = 4 -> LB = 0: the hand-off stays inside each wave
             ntt_pass<LOGM, LT, W, 6, 4, false, false, true, TWM, NoEpilogue&, true, Q30>(lds, twm, q, qni, (W)0, (W)0, tid, prefix, none);
         } else {
@@ -498,7 +491,7 @@ k_ks_accum_half(DevRing<u32> R, const u32* __restrict__ a, const u32* __restrict
             KS_STAMP(4);                          // LDS pass 1
             KS_SYNC();
             KS_STAMP(5);
-            if (!KS_DBG(32u)) ntt_pass<LOGM, LT, W, 6, 4, false, false, ALCH_KS_SERIAL, TWF, NoEpilogue&, true, Q30>(lds, twf, q, qni, (W)0, (W)0, tid, prefix, none);
+            if (!KS_DBG(32u)) ntt_pass<LOGM, LT, W, 6, 4, false, false, ALCH_KS_SERIAL, TW4, NoEpilogue&, true, Q30>(lds, tw4, q, qni, (W)0, (W)0, tid, prefix, none);
             KS_STAMP(6);                          // LDS pass 2
             pair_sync<LOGM>();                    // LB = 4 -> LB = 0: the hand-off stays inside each wave
             KS_STAMP(7);

@@ -175,7 +175,7 @@ k_rescale_keep_half(DevRing<W> R, const W* __restrict__ src, const typename Sign
             *reinterpret_cast<V*>(&lds[swz<LOGM>(idx)]) = u0;
         }
     }
-    const auto tw = fwd_tw(R, t);
+    const auto tw = fwd_tw_shared(R, t);
     const auto twm = fwd_twm(R, t);
     const W Ct = D.comb_m[0][t];
 #pragma unroll 1
@@ -192,7 +192,7 @@ k_rescale_keep_half(DevRing<W> R, const W* __restrict__ src, const typename Sign
         lds_barrier();
         ntt_pass<LOGM, LT, W, F, 4, false, false, false>(lds, tw, q, qni, (W)0, (W)0, tid, prefix, none);
         lds_barrier();
-        ntt_pass<LOGM, LT, W, F + 4, 4, false, false, false>(lds, tw, q, qni, (W)0, (W)0, tid, prefix, none);
+        ntt_pass<LOGM, LT, W, F + 4, 4, false, false, false>(lds, fwd_pass_tw<4, T>(tw, twm), q, qni, (W)0, (W)0, tid, prefix, none);
         pair_sync<LOGM>();
         ntt_pass<LOGM, LT, W, F + 8, 4, false, false, false>(lds, twm, q, qni, (W)0, (W)0, tid, prefix, none);
         lds_barrier();

@@ -13,7 +13,10 @@
 //             written to LDS; their three twiddles (a pair and a single word, lane-contiguous in the table) are
 //             fetched with the piece's operands.
 //   LB = 2    stages [8, 12): groups {64 h + lo + 4 k}, per-lane twiddles (four lanes share a group index)
-//   LB = 6    stages [4, 8):  wave-uniform twiddles
+//   LB = 6    stages [4, 8):  wave-uniform twiddles.  ALCH_PLANT3_INV (!Q30): Plantard constants (R.twpi), the pass enters with the
+//             12-instruction butterfly on the lazy [0,2q) values of the LB = 2 pass and goes on with the 8-instruction one on values
+//             kept in [0, q] (modarith.hpp); so does the LB = 10 pass, and the closing stage takes keep[] and x[] as they are:
+//             u + y <= 2q and u - y + q <= 2q are plain words for the Montgomery products that carry n^-1 s.
 //   LB = 10   stages [0, 4):  wave-uniform twiddles, KEEP: nothing is written back.  A lane owns the coefficients
 //             tid + 512 g + 1024 k of its half -- the same set for both halves -- so half 0's 32 values wait in
 //             registers while half 1 is transformed, and stage 0, the n^-1 s scaling, the centred lift and the digit
@@ -24,6 +27,7 @@
 // and that closing trip: five), == 3 its radix-32 form.  DESIGN.md section 11 has the measurements.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "ntt_engine.hpp"
 
 #ifndef ALCH_TI_SPLIT_PASSES
@@ -87,7 +91,9 @@ k_tensor_intt_split(DevRing<u32> R, const u32* __restrict__ a, const u32* __rest
 #endif
 
     for (unsigned item = blockIdx.x; item < nitems; item += gridDim.x) {
-        const u32 ct = item / (unsigned)L, i = item % (unsigned)L;
+        // the quotient comes out of the vector unit (the division runs on a float reciprocal): hand it back to scalar registers here,
+        // or every offset derived from it may stay in vector registers (buffer offsets then cost a loop per access)
+        const u32 ct = __builtin_amdgcn_readfirstlane(item / (unsigned)L), i = item - ct * (unsigned)L;
         const ModP<W> m = R.mod[i];
         const W q = m.q, qni = m.qni;
         const W ninv_s = mont_mul(R.ninv_m[i], spre.v[i], m), w1ninv_s = mont_mul(R.w1ninv_m[i], spre.v[i], m);
@@ -95,6 +101,10 @@ k_tensor_intt_split(DevRing<u32> R, const u32* __restrict__ a, const u32* __rest
         const u32 drow = (ct * (u32)L + i) * ROW;
         const int rot = (int)((item ^ (item >> 3)) & (NV - 1));      // slice order rotated per item (HBM channels)
         const W* twi = R.twi[i];
+        // the two wave-uniform passes: Plantard constants, values in [0, q] (the closing stage then skips its reductions)
+        constexpr bool PINV = ALCH_PLANT3_INV && ALCH_TI_EPI_REGS && !Q30;
+        const auto twu = pick_tw<PINV>(R.twpi[i], R.twi[i]);
+        typedef typename std::remove_cv<typename std::remove_pointer<decltype(twu)>::type>::type TWU;
         W keep[G::E];
 #pragma unroll 1
         for (int half = 0; half < 2; ++half) {
@@ -165,7 +175,7 @@ k_tensor_intt_split(DevRing<u32> R, const u32* __restrict__ a, const u32* __rest
 #if ALCH_TI_ONLOAD
             ntt_pass<LOGM, LT, W, 8, 4, true, false, false, W, NoEpilogue&, false, Q30>(lds, twi, q, qni, (W)0, (W)0, tid, prefix, none);
             lds_barrier();
-            ntt_pass<LOGM, LT, W, 4, 4, true, false, false, W, NoEpilogue&, false, Q30>(lds, twi, q, qni, (W)0, (W)0, tid, prefix, none);
+            ntt_pass<LOGM, LT, W, 4, 4, true, false, false, TWU, NoEpilogue&, false, Q30, PINV>(lds, twu, q, qni, (W)0, (W)0, tid, prefix, none);
             lds_barrier();
 #if ALCH_TI_CLOSE_LDS
             ntt_pass<LOGM, LT, W, 0, 4, true, false, false, W, NoEpilogue&, false, Q30>(lds, twi, q, qni, (W)0, (W)0, tid, prefix, none);
@@ -180,7 +190,8 @@ k_tensor_intt_split(DevRing<u32> R, const u32* __restrict__ a, const u32* __rest
                 } else {
 #pragma unroll
                     for (int k = 0; k < 16; ++k) {
-                        const W u = csub(keep[16 * g + k], q), y = csub(x[k], q);
+                        // PINV: both in [0, q] already; the sums below stay words (<= 2q) and the products take any word
+                        const W u = PINV ? keep[16 * g + k] : csub(keep[16 * g + k], q), y = PINV ? x[k] : csub(x[k], q);
                         const W c0 = csub(mont_mul_lazy((W)(u + y), ninv_s, q, qni), q);
                         const W c1 = csub(mont_mul_lazy((W)(u - y + q), w1ninv_s, q, qni), q);
                         const int32_t z0 = c0 > hq ? (int32_t)c0 - (int32_t)q : (int32_t)c0;
@@ -191,7 +202,7 @@ k_tensor_intt_split(DevRing<u32> R, const u32* __restrict__ a, const u32* __rest
                     }
                 }
             };
-            ntt_pass<LOGM, LT, W, 0, 4, true, true, false, W, decltype(close)&, false, Q30>(lds, twi, q, qni, (W)0, (W)0, tid, prefix, close);
+            ntt_pass<LOGM, LT, W, 0, 4, true, true, false, TWU, decltype(close)&, false, Q30>(lds, twu, q, qni, (W)0, (W)0, tid, prefix, close);
 #endif
 #elif ALCH_TI_SPLIT_PASSES == 3
             // 14 stages as 5 + 5 + 4: three LDS round trips per half instead of four (radix-32 groups: 32 coefficients and

@@ -31,22 +31,27 @@ struct DevRing {
     const W* twf[MAXL];  // forward twiddles (device, Montgomery form), n words
     const W* twi[MAXL];  // inverse twiddles
     const u64* twp[MAXL]; // forward twiddles as Plantard constants (32-bit rings only), n x 8 bytes
+    const u64* twpi[MAXL]; // inverse twiddles likewise (32-bit rings only)
     const Sh64* tws[MAXL];  // 64-bit rings: forward twiddles as Shoup pairs (plain residue, floor(w 2^64 / q)), n x 16 bytes
     const Sh64* twsi[MAXL]; // 64-bit rings: inverse twiddles likewise
 };
 
-// Forward-transform twiddle table of limb j.  ALCH_USE_PLANTARD=1 switches 32-bit rings to Plantard constants
-// (9-instruction butterfly instead of 10, two-word twiddles).  Measured on MI355X (interleaved A/B runs of
-// bench.py): 9 % fewer VALU instructions in k_ks_accum_half but 2 % LOWER throughput -- the early passes get
-// faster and the hint/digit-load phases slower by the same amount -- so the default stays Montgomery.
-#ifndef ALCH_USE_PLANTARD
-#define ALCH_USE_PLANTARD 0
-#endif
-#if ALCH_USE_PLANTARD
-__device__ __forceinline__ const u64* fwd_tw(const DevRing<u32>& R, int j) { return R.twp[j]; }
-#else
+// Forward-transform twiddle tables of limb j.  fwd_tw: what ntt_forward's shared-twiddle passes read (32-bit rings: Montgomery words).
+// fwd_tw_shared: the same for the kernels that pick a table per pass (fwd_pass_tw, ntt_engine.hpp) -- 32-bit rings: Plantard
+// constants (ALCH_PLANT3_FWD, the product: 7-instruction butterfly, two-word twiddles in scalar registers), the Montgomery table in
+// -DALCH_PLANT3_FWD=0 builds.  Q30 instantiations never read Plantard constants: they keep the Montgomery table and bfly_fwd4 in
+// every pass (ntt_pass refuses any other twiddle word for them).
+// History.  ALCH_USE_PLANTARD once switched every shared-twiddle pass to the four-instruction Plantard product: a 9-instruction
+// butterfly against the then 10-instruction Montgomery one, 9 % fewer VALU instructions in k_ks_accum_half and -2 % (round 2),
+// +0.4 .. +1.3 % (round 4) on the headline.  The macro now only selects that four-instruction product inside the Plantard
+// butterflies (modarith.hpp, plant_tw) for A/B builds; which passes read Plantard tables is decided by the ALCH_PLANT3_* switches.
 __device__ __forceinline__ const u32* fwd_tw(const DevRing<u32>& R, int j) { return R.twf[j]; }
+#if ALCH_PLANT3_FWD
+__device__ __forceinline__ const u64* fwd_tw_shared(const DevRing<u32>& R, int j) { return R.twp[j]; }
+#else
+__device__ __forceinline__ const u32* fwd_tw_shared(const DevRing<u32>& R, int j) { return R.twf[j]; }
 #endif
+__device__ __forceinline__ const Sh64* fwd_tw_shared(const DevRing<u64>& R, int j) { return R.tws[j]; }
 __device__ __forceinline__ const Sh64* fwd_tw(const DevRing<u64>& R, int j) { return R.tws[j]; }
 // table of the forward transform's last pass (per-lane twiddles) and of the inverse transform
 __device__ __forceinline__ const u32* fwd_twm(const DevRing<u32>& R, int j) { return R.twf[j]; }

@@ -4,7 +4,9 @@
 // Measured on MI355X (tools/ubench): v_mul_lo/v_mul_hi/v_mad_u64_u32 all issue at ~4.5 cycles per
 // wave64, v_add/v_sub at ~2.6, v_min_u32 at ~4.1.  The 32-bit Montgomery product below compiles to
 // exactly three multiplier instructions (v_mad_u64_u32, v_mul_lo_u32, v_mad_u64_u32) with no
-// separate add, one fewer instruction than Shoup's and with one-word twiddles.
+// separate add, one fewer instruction than Shoup's and with one-word twiddles.  A product by a table constant in
+// Plantard's form (plant_mul3 below) is three multiplier instructions as well and comes out in [0, q] with no
+// conditional subtraction: the butterflies whose twiddle is shared by a whole wave use it (two-word twiddles).
 //
 // Ranges.  mont_mul_lazy(a, b): a any word, b < q  ->  a*b*R^-1 mod q in [0, 2q).
 // Ring data are kept "lazy" in [0, 2q) between butterfly stages (2q < 2^32 / 2^63); csub() brings
@@ -163,27 +165,65 @@ ALCH_HD void stage01_signed(int32_t x0, int32_t x1, int32_t x2, int32_t x3, int3
 }
 
 // Plantard multiplication by a precomputed constant (Plantard, "Efficient word size modular arithmetic",
-// 2021).  For a constant c the table holds  br = (-c * 2^64 mod q) * q^-1 mod 2^64.  With T = a*br mod 2^64,
-//   result = floor(((T >> 32) + 1) * q / 2^32)  ==  a*c mod q,   exactly reduced, for ANY 32-bit a
+// 2021).  For a constant c the table holds  br = (-c * 2^64 mod q) * q^-1 mod 2^64.  With T = a*br mod 2^64 and t1 = T >> 32,
+//   result = floor((t1 + 1) * q / 2^32)  ==  a*c mod q   for ANY 32-bit a
 // provided q < 2^31 (then a * (-c 2^64 mod q) < 2^63 and q 2^32 + that product < 2^64, which is the
-// condition for the rounded quotient to be exact).  Four instructions and no correction step, against five
-// for Montgomery + conditional subtract; the price is a two-word constant.
-ALCH_HD u32 plant_mul(u32 a, u64 br, u32 q) {
+// condition for the rounded quotient to be exact).  The price is a two-word constant.
+// plant_mul3: the closing step as hi32(t1 q + q), ONE v_mad_u64_u32 -- three multiplier instructions in all (v_mul_hi_u32 and two
+// v_mad_u64_u32), as many as a lazy Montgomery product, and the result needs no correction: it lies in [0, q].  The upper end is
+// reached only at t1 = 2^32 - 1 (a c = 0 mod q), where (t1 + 1) q / 2^32 is q itself; every consumer of these butterflies takes q
+// for 0 (the next butterfly, csub, a Montgomery product).
+// plant_mul: the same with t1 + 1 formed in 32 bits first (four instructions; at t1 = 2^32 - 1 it wraps to 0 where plant_mul3 gives
+// q, otherwise the same word).  Kept for A/B builds (ALCH_USE_PLANTARD, kernels_ntt.hpp).
+ALCH_HD u32 plant_close(u32 t1, u32 q) { return (u32)(((u64)t1 * q + q) >> 32); }     // (2^32 - 1) q + q = q 2^32: no overflow
+ALCH_HD u32 plant_t1(u32 a, u64 br) {
     const u64 lo = (u64)a * (u32)br;
-    const u32 t1 = (u32)((u64)a * (u32)(br >> 32) + (lo >> 32));
+    return (u32)((u64)a * (u32)(br >> 32) + (lo >> 32));
+}
+ALCH_HD u32 plant_mul3(u32 a, u64 br, u32 q) { return plant_close(plant_t1(a, br), q); }
+ALCH_HD u32 plant_mul(u32 a, u64 br, u32 q) {
+    const u32 t1 = plant_t1(a, br);
 #if defined(__HIP_DEVICE_COMPILE__)
     return __umulhi(t1 + 1u, q);
 #else
     return (u32)(((u64)(u32)(t1 + 1u) * q) >> 32);
 #endif
 }
+// the product the Plantard butterflies use: plant_mul3 unless an A/B build asks for the four-instruction form
+#ifndef ALCH_USE_PLANTARD
+#define ALCH_USE_PLANTARD 0
+#endif
+ALCH_HD u32 plant_tw(u32 a, u64 br, u32 q) {
+#if ALCH_USE_PLANTARD
+    return plant_mul(a, br, q);
+#else
+    return plant_mul3(a, br, q);
+#endif
+}
 
-// Forward butterfly with a Plantard twiddle: 9 VALU instructions.  x,y in [0,2q) -> outputs in [0,2q].
-ALCH_HD void bfly_fwd(u32& x, u32& y, u64 br, u32 q, u32 /*qni*/) {
+// Forward butterfly with a Plantard twiddle: 7 VALU instructions (csub 2, product 3, add, v_sad_u32).  x in [0,2q), y ANY word
+// -> xx < q, t <= q:  x' = xx + t <= 2q - 1,  y' = |q - t| + xx <= 2q - 1: both below 2q, what a Montgomery pass, another
+// Plantard butterfly or the hint product takes.
+// (its two legs from the twiddle product t in [0, q], apart so that the host test can put t = q through them)
+ALCH_HD void bfly_fwd_from_t(u32& x, u32& y, u32 t, u32 q) {
     const u32 xx = csub(x, q);
-    const u32 t = plant_mul(y, br, q);
     x = xx + t;
-    y = xx + (q - t);
+    y = diff_leg(xx, q, t);
+}
+ALCH_HD void bfly_fwd(u32& x, u32& y, u64 br, u32 q, u32 /*qni*/) { bfly_fwd_from_t(x, y, plant_tw(y, br, q), q); }
+
+// Inverse (Gentleman-Sande) butterfly with a Plantard twiddle on values kept in [0, q] (q itself stands for 0): 8 VALU instructions.
+//   d = x + (q - y) in [0, 2q] (any word suits the product),  x' = csub(x + y, q) in [0, q]  (x + y <= 2q),  y' = d w in [0, q].
+ALCH_HD void bfly_inv(u32& x, u32& y, u64 br, u32 q, u32 /*qni*/) {
+    const u32 s = x + y, d = x + (q - y);
+    x = csub(s, q);
+    y = plant_tw(d, br, q);
+}
+// its entry form: x, y lazy in [0,2q) are reduced first (12 instructions); outputs in [0, q] as above.
+ALCH_HD void bfly_inv_entry(u32& x, u32& y, u64 br, u32 q, u32 qni) {
+    x = csub(x, q);
+    y = csub(y, q);
+    bfly_inv(x, y, br, q, qni);
 }
 
 // Inverse (Gentleman-Sande) butterfly: x' = x + y, y' = (x - y) * w.  in/out in [0,2q).

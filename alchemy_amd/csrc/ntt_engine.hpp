@@ -17,9 +17,43 @@
 // R contiguous words per lane and moves them with 128-bit LDS accesses.  The XOR swizzle swz() keeps
 // every one of those access patterns bank-conflict free without padding.
 #pragma once
+#include <type_traits>
 #include "modarith.hpp"
 
+// Which butterflies of 32-bit rings take Plantard twiddles (two-word constants, plant_mul3 in modarith.hpp); one switch per part,
+// tools/build_variant.sh builds the others for A/B runs.  DESIGN.md section 11 has the counts and the measurements.
+//   ALCH_PLANT3_FWD      forward passes whose twiddles are wave-uniform (LB >= 6: the pair sits in scalar registers) and stage 2 of
+//                        k_ks_accum_half's pass G: 7 instructions per butterfly instead of 9.  In the kernels that run two half-size
+//                        workgroups per CU (k_ks_accum_half, k_crt_half, k_rescale_*_half); the others keep Montgomery words: with
+//                        two-word twiddles several of them lose a wave per SIMD or spill by the compiler's figure
+//   ALCH_PLANT3_FWD_LB4  also the forward pass with LB = 4 (sixteen lanes share a twiddle; its per-lane loads become 8-byte)
+//   ALCH_PLANT3_INV      k_tensor_intt_split's two wave-uniform inverse passes on values kept in [0, q]: 8 instructions instead of 10
+// The per-lane passes (LB = 0, LB = 2) keep one-word Montgomery twiddles: two-word constants would double their load traffic and
+// twiddle registers.  Q30 instantiations keep the Montgomery table and Harvey's butterflies in every pass.
+#ifndef ALCH_PLANT3_FWD
+#define ALCH_PLANT3_FWD 1
+#endif
+#ifndef ALCH_PLANT3_FWD_LB4
+#define ALCH_PLANT3_FWD_LB4 0
+#endif
+#ifndef ALCH_PLANT3_INV
+#define ALCH_PLANT3_INV 1
+#endif
+
 namespace alch {
+
+// does the forward pass with stride bits LB of a T-thread workgroup read the shared-twiddle table `tw` (else the per-lane table `twm`)?
+template <int LB, int T>
+constexpr bool plant_fwd_pass() { return (LB >= 6 && T >= 64) || (ALCH_PLANT3_FWD_LB4 && LB == 4); }
+template <bool FIRST, typename A, typename B>
+__host__ __device__ __forceinline__ auto pick_tw(A a, B b) {
+    if constexpr (FIRST) return a; else return b;
+}
+// the table a forward pass with stride bits LB reads: tw where it shares its twiddles (or where both tables are one), else twm
+template <int LB, int T, typename TW, typename TWM>
+__device__ __forceinline__ auto fwd_pass_tw(const TW* tw, const TWM* twm) {
+    return pick_tw<std::is_same<TW, TWM>::value || plant_fwd_pass<LB, T>()>(tw, twm);
+}
 
 template <int LOGN, int LOGT_ = -1>
 struct Geo {
@@ -169,8 +203,10 @@ struct NoEpilogue {
 // stage 0 is not the transform's stage 0 passes FOLD = false.
 // Q30 (32-bit rings whose moduli are all below 2^30, Montgomery twiddles): Harvey's butterflies -- forward values stay lazy in [0,4q)
 // from pass to pass (callers' epilogues multiply them, which takes any word, or reduce them), inverse values in [0,2q) as otherwise.
+// PENTRY (inverse passes with Plantard twiddles only): the pass's inputs are lazy in [0,2q) and its first stage reduces them
+// (bfly_inv_entry); without it the inputs are already in [0, q].  Either way the outputs are in [0, q].
 template <int LOGN, int LOGT, typename W, int S0, int NS, bool INVERSE, bool KEEP, bool SERIAL, typename TW, typename Epi,
-          bool FOLD = true, bool Q30 = false>
+          bool FOLD = true, bool Q30 = false, bool PENTRY = false>
 __device__ __forceinline__ void ntt_pass(W* __restrict__ lds, const TW* __restrict__ tw, W q, W qni,
                                          W ninv_m, W w1ninv_m, int t, int prefix, Epi&& epi) {
     typedef Geo<LOGN, LOGT> G;
@@ -179,6 +215,12 @@ __device__ __forceinline__ void ntt_pass(W* __restrict__ lds, const TW* __restri
     constexpr int NG = G::E / R;                     // groups per thread
     static_assert(NG >= 1, "group larger than the per-thread coefficient budget");
     static_assert(NS >= 1 && NS <= 5, "one to five stages per pass");
+    // two-word Plantard constants on a 32-bit ring: never with Harvey's butterflies (they would read half a constant as a twiddle),
+    // and an inverse pass on [0, q] values has no n^-1 fold
+    constexpr bool PLANT = std::is_same<TW, u64>::value && std::is_same<W, u32>::value;
+    static_assert(!Q30 || std::is_same<TW, W>::value, "Q30 passes take the one-word Montgomery table");
+    static_assert(!(PLANT && INVERSE && FOLD && S0 == 0), "Plantard inverse passes leave stage 0's n^-1 fold to the caller");
+    static_assert(PLANT || !PENTRY, "PENTRY belongs to Plantard inverse passes");
     typedef typename Vec4<W>::type V;
     constexpr int VL = Vec4<W>::LANES;
     // all 64 lanes of a wave share h when a run of equal h covers a whole wave
@@ -255,6 +297,9 @@ __device__ __forceinline__ void ntt_pass(W* __restrict__ lds, const TW* __restri
                         x[k + half] = mont_mul_lazy((W)(a - b + q), w1ninv_m, q, qni);
                     } else if constexpr (Q30) {
                         bfly_inv4(x[k], x[k + half], w[k >> (NS - r)], q, qni);
+                    } else if constexpr (PLANT) {
+                        if (PENTRY && r == NS - 1) bfly_inv_entry(x[k], x[k + half], w[k >> (NS - r)], q, qni);
+                        else bfly_inv(x[k], x[k + half], w[k >> (NS - r)], q, qni);
                     } else {
                         bfly_inv(x[k], x[k + half], w[k >> (NS - r)], q, qni);
                     }
@@ -310,11 +355,12 @@ __device__ __forceinline__ void ntt_forward(W* lds, const TW* tw, const TWM* twm
                                             int prefix = 1) {
     // prefix != 1: the transform is one half of a transform twice its size whose stage 0 ran elsewhere
     // (k_crt_split); tw / twm are then the tables of the big ring.
-    // tw : twiddle table for the passes whose twiddles are shared by many lanes (Plantard constants on 32-bit
-    //      rings: one instruction less per butterfly, fetched by scalar or broadcast loads);
-    // twm: Montgomery table for the last pass, where every lane needs its own 15 twiddles and two-word
-    //      constants would double the per-lane load traffic and register pressure (64-bit rings: Shoup pairs in every
-    //      pass -- a two-word twiddle still beats a 27-instruction Montgomery product).
+    // tw : twiddle table for the passes whose twiddles are shared by many lanes;
+    // twm: table for the last pass, where every lane needs its own 15 twiddles.
+    // 32-bit rings: the Montgomery table for both (the kernels that read Plantard constants in their shared-twiddle passes --
+    // k_ks_accum_half, k_crt_half, the half-size rescale kernels -- call ntt_pass themselves and pick the table per pass with
+    // fwd_pass_tw); 64-bit rings: Shoup pairs in every pass -- a two-word twiddle still beats a 27-instruction Montgomery product.
+    static_assert(std::is_same<TW, TWM>::value || !std::is_same<W, u32>::value, "32-bit rings: one-word twiddles in every pass here");
     typedef Geo<LOGN> G;
     constexpr int P = G::NPASS, F = G::NS0, LT = G::LOGT;
     NoEpilogue none;

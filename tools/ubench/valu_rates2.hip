@@ -11,7 +11,7 @@ constexpr int UNROLL = 16;
 
 enum Op { ADD_VV, ADD_VS, MIN_VV, MIN_VS, MAX_VS, MINI_VS, CMP_CND, SUBCO_CND, ADD3, LSHLADD, AND_VS, ASHR, MED3,
           DPP_ROR8, DPP_QP, DPP_MIRROR, PERMLANE32, SWIZZLE, BPERMUTE, MOV, BF_STRICT_MIN, BF_STRICT_CND, BF_X1Q, BF_LAZY30,
-          SAD_SVV, ADD_SUB_PAIR, BF_SAD,
+          SAD_SVV, ADD_SUB_PAIR, BF_SAD, MAD64_HI, BF_PLANT3, BF_INV, BF_INV_PLANT3,
           LDS_R32, LDS_W32, LDS_R128, LDS_W128, NOPS };
 
 template <int OP>
@@ -23,6 +23,7 @@ __global__ void __launch_bounds__(256) k_rate(uint32_t* out, uint32_t seed, uint
     for (int i = threadIdx.x; i < 256 * 36; i += 256) lds[i] = i * seed;
     __syncthreads();
     uint32_t w = seed | 1u;
+    const uint32_t brl = seed * 2654435761u, brh = seed * 40503u + 7u;     // a two-word twiddle: wave-uniform, scalar registers
     const uint32_t q2 = 2u * q;
     uint32_t laddr = threadIdx.x * 4;          // ds_*_b32 byte address: conflict-free
     uint32_t laddr128 = threadIdx.x * 144;     // padded row for b128
@@ -105,6 +106,33 @@ __global__ void __launch_bounds__(256) k_rate(uint32_t* out, uint32_t seed, uint
                 t = min(t, t - q);
                 uint32_t xx = min(x[i], x[i] - q);
                 x[i] = xx + t; y[i] = (q > t ? q - t : t - q) + xx;
+            }
+            else if constexpr (OP == MAD64_HI) {           // hi32(x q + q): the closing step of the three-instruction Plantard product
+                x[i] = (uint32_t)(((unsigned long long)x[i] * q + q) >> 32);
+            }
+            else if constexpr (OP == BF_PLANT3) {
+                // forward butterfly with a Plantard twiddle: csub, v_mul_hi_u32 + 2 v_mad_u64_u32, add, v_sad_u32: 7 instructions
+                const unsigned long long lo = (unsigned long long)y[i] * brl;
+                const uint32_t t1 = (uint32_t)((unsigned long long)y[i] * brh + (lo >> 32));
+                const uint32_t t = (uint32_t)(((unsigned long long)t1 * q + q) >> 32);
+                uint32_t xx = min(x[i], x[i] - q);
+                x[i] = xx + t; y[i] = (q > t ? q - t : t - q) + xx;
+            }
+            else if constexpr (OP == BF_INV) {
+                // the inverse butterfly of the kernels: two csubs, add, subtract + add, lazy Montgomery product: 10 instructions
+                const uint32_t a = min(x[i], x[i] - q), b = min(y[i], y[i] - q);
+                x[i] = a + b;
+                unsigned long long p = (unsigned long long)(a - b + q) * w;
+                uint32_t m = (uint32_t)p * qinv;
+                y[i] = (uint32_t)((p + (unsigned long long)m * q) >> 32);
+            }
+            else if constexpr (OP == BF_INV_PLANT3) {
+                // inverse butterfly on values kept in [0, q] with a Plantard twiddle: 8 instructions
+                const uint32_t sm = x[i] + y[i], d = x[i] + (q - y[i]);
+                x[i] = min(sm, sm - q);
+                const unsigned long long lo = (unsigned long long)d * brl;
+                const uint32_t t1 = (uint32_t)((unsigned long long)d * brh + (lo >> 32));
+                y[i] = (uint32_t)(((unsigned long long)t1 * q + q) >> 32);
             }
             else if constexpr (OP == BF_LAZY30) {
                 unsigned long long p = (unsigned long long)y[i] * w;
@@ -189,6 +217,10 @@ int main() {
         run<SAD_SVV>("sad_u32 s,v,v", w);
         run<ADD_SUB_PAIR>("add v,s+sub vv", w);
         run<BF_SAD>("bf sad", w);
+        run<MAD64_HI>("mad_u64 hi", w);
+        run<BF_PLANT3>("bf plant3", w);
+        run<BF_INV>("bf inv", w);
+        run<BF_INV_PLANT3>("bf inv plant3", w);
     }
     return 0;
 }
