@@ -115,3 +115,17 @@ def ct_automorph_hoisted(aset: AutomorphSet, ct: Buf, batch: int, s_pre=None, ou
     sp = _pu64(s_pre) if s_pre is not None else None
     _check(aset.ring._l.alch_ct_automorph_hoisted(aset._h, ct._h, out._h, batch, sp, ALCH_AUTO_SUM if sum else 0))
     return out if meta is None else (out, meta)
+
+
+# ---- weighted sums of hoisted rotations: the diagonals of a slot-wise linear map (include/alchemy_hip.h, "Weighted sums of hoisted rotations")
+def ct_automorph_lincomb(aset: AutomorphSet, weights: Buf, ct: Buf, batch: int, n_out: int = 1, w_first: int = 0, s_pre=None,
+                         out: Buf | None = None, meta=None):
+    """out[g * batch + b] = sum_r weights[w_first + g R + r] (.) keySwitch(sigma_(j_r)(ct[b])), g < n_out, over the R units of the set
+    at ONE decomposition of the batch: `weights` holds n_out * R public CRT-basis elements (canonical residues), read at call time.
+    Linear ciphertexts (k = 0), CRT basis in and out; s_pre as in ct_automorph.  Returns the result buffer (a new one unless `out` is
+    given), or (buffer, meta) when a CtMeta is passed (unchanged, as in ct_automorph_hoisted: a public product keeps k, l and p)."""
+    if out is None:
+        out = aset.ring.alloc(max(1, 2 * batch * n_out))
+    sp = _pu64(s_pre) if s_pre is not None else None
+    _check(aset.ring._l.alch_ct_automorph_lincomb(aset._h, weights._h, w_first, n_out, ct._h, out._h, batch, sp, 0))
+    return out if meta is None else (out, meta)

@@ -56,6 +56,7 @@ SYMBOLS = [
     "alch_ring_set_rng_key", "alch_ring_rng", "alch_rng_words",
     "alch_automorph_table", "alch_buf_automorph", "alch_automorph_create", "alch_automorph_free", "alch_ct_automorph",
     "alch_automorph_set_create", "alch_automorph_set_free", "alch_ct_automorph_hoisted",
+    "alch_ct_automorph_lincomb",
 ]
 
 
@@ -210,6 +211,7 @@ def load_library():
         "alch_automorph_set_create": [VP, C.c_uint32, C.POINTER(C.c_uint32), C.c_int, VP, C.POINTER(VP)],
         "alch_automorph_set_free": [VP],
         "alch_ct_automorph_hoisted": [VP, VP, VP, C.c_size_t, PU64, C.c_uint],
+        "alch_ct_automorph_lincomb": [VP, VP, C.c_size_t, C.c_size_t, VP, VP, C.c_size_t, PU64, C.c_uint],
     }
     for name, args in sig.items():
         fn = getattr(l, name, None)

@@ -1327,6 +1327,7 @@ __global__ void k_checksum(const W* data, size_t words, u64* sum, u64 w0) {
 #include "kernel_rlwe.hpp"
 #include "kernel_automorph.hpp"
 #include "kernel_hoist.hpp"
+#include "kernel_lincomb.hpp"
 
 static inline unsigned ew_grid(size_t items) {
     size_t g = (items + 255) / 256;
@@ -4247,8 +4248,11 @@ static void launch_hoist_mac(alch_ring* r, W* po, const W* dig, const W* cin, si
                            r0, nrot, 0, sm, sc);
 }
 
-template <typename W>
-static int do_hoisted(const alch_automorph_set* a, const void* in, void* out, size_t batch, const uint64_t* s_pre, bool sum) {
+// The walk both hoisted calls share: per chunk of at most "scratch_mib", the digits of s_pre c1 in CRT form, then
+// body(done, now, GD, digits, cin, S, sm, scale) queues the inner products over the GD digits of the chunk's `now` ciphertexts from
+// ciphertext `done` on.
+template <typename W, typename Body>
+static int hoist_walk(const alch_automorph_set* a, const void* in, size_t batch, const uint64_t* s_pre, Body body) {
     alch_ring* r = a->ring;
     const int L = r->L;
     const u32 bw = (u32)gadget_width(a->gadget);      // BaseBGad 2^bw; 0: TrivGad
@@ -4266,7 +4270,7 @@ static int do_hoisted(const alch_automorph_set* a, const void* in, void* out, si
     if (rc != ALCH_OK) return rc;
     Carve cv(r->ws_full.p, chunk);
     char *win = cv.take(2 * eb), *x0 = cv.take(x0_b), *x1 = cv.take(x1_b), *dig = cv.take(dig_b);
-    if (!cv.matches(per_ct)) return fail(ALCH_E_INTERNAL, "do_hoisted: the scratch carve differs from the bytes reserved per ciphertext");
+    if (!cv.matches(per_ct)) return fail(ALCH_E_INTERNAL, "hoist_walk: the scratch carve differs from the bytes reserved per ciphertext");
     uint64_t s_eff[MAXL] = {0};
     for (int i = 0; i < L; ++i) s_eff[i] = up_scalar(r, 0, i, s_pre ? s_pre[i] : 1);
     const bool scale = s_pre != nullptr;
@@ -4296,8 +4300,16 @@ static int do_hoisted(const alch_automorph_set* a, const void* in, void* out, si
             HIP_TRY(hipGetLastError());
             if ((rc = gen_digit_tail<W>(r, r, x1, dig, now, GD, (u32)L, 0u, bw, b2first, b2kd)) != ALCH_OK) return rc;
         }
-        const W* cin = reinterpret_cast<const W*>(src);
-        const W* pd = reinterpret_cast<const W*>(dig);
+        if ((rc = body(done, now, GD, reinterpret_cast<const W*>(dig), reinterpret_cast<const W*>(src), S, sm, scale)) != ALCH_OK) return rc;
+    }
+    return ALCH_OK;
+}
+
+template <typename W>
+static int do_hoisted(const alch_automorph_set* a, const void* in, void* out, size_t batch, const uint64_t* s_pre, bool sum) {
+    alch_ring* r = a->ring;
+    const size_t eb = elem_bytes(r);
+    return hoist_walk<W>(a, in, batch, s_pre, [&](size_t done, size_t now, u32 GD, const W* pd, const W* cin, const HoistSet<W>& S, const Scal<W>& sm, bool scale) -> int {
         if (sum) {
             launch_hoist_mac<W>(r, reinterpret_cast<W*>(reinterpret_cast<char*>(out) + done * 2 * eb), pd, cin, now, GD, S, 0u, a->n_j, sm, scale);
             HIP_TRY(hipGetLastError());
@@ -4308,8 +4320,8 @@ static int do_hoisted(const alch_automorph_set* a, const void* in, void* out, si
                 HIP_TRY(hipGetLastError());
             }
         }
-    }
-    return ALCH_OK;
+        return ALCH_OK;
+    });
 }
 
 extern "C" int alch_ct_automorph_hoisted(const void* handle, const alch_buf* in, alch_buf* out, size_t batch, const uint64_t* s_pre, unsigned flags) try {
@@ -4329,6 +4341,67 @@ extern "C" int alch_ct_automorph_hoisted(const void* handle, const alch_buf* in,
     if (bytes_overlap(out->dptr, 2 * rots * batch * eb, in->dptr, 2 * batch * eb)) return fail(ALCH_E_INVALID, "alch_ct_automorph_hoisted: out must not alias the input");
     BIND(r);
     return ALCH_BY_WORD(r, do_hoisted, a, in->dptr, out->dptr, batch, s_pre, sum);
+} catch (...) { return abi_catch(); }
+
+// ------------------------------------------------------------------------------------------------------
+// Weighted sums of hoisted rotations (include/alchemy_hip.h, "Weighted sums of hoisted rotations"; kernel_lincomb.hpp)
+// ------------------------------------------------------------------------------------------------------
+// rows [0, nrows) of one row block over the chunk's `now` ciphertexts: the forms and the dispatch of launch_hoist_mac
+template <typename W>
+static void launch_hoist_lincomb(alch_ring* r, W* po, const W* dig, const W* cin, size_t now, u32 D, const HoistSet<W>& S, u32 nrot, const Scal<W>& sm,
+                                 bool scale, const W* wts, u32 nrows, size_t ostride) {
+    constexpr int VL = Vec4<W>::LANES, TL = LINCOMB_TILE, RW = LINCOMB_ROWS;
+    const size_t tiles = (now + TL - 1) / TL * (size_t)r->L;
+    const int sc = scale ? 1 : 0;
+    if (!r->gen)                                   // n >= 16: a multiple of the vector width
+        hipLaunchKernelGGL((k_hoist_lincomb<W, VL, TL, true, RW>), dim3(ew_grid(tiles * (r->n / VL))), dim3(256), 0, r->stream, dev_ring<W>(r), po, dig, cin,
+                           now, D, S, nrot, r->logn, sm, sc, wts, nrows, ostride);
+    else if (r->n % VL == 0)
+        hipLaunchKernelGGL((k_hoist_lincomb<W, VL, TL, false, RW>), dim3(ew_grid(tiles * (r->n / VL))), dim3(256), 0, r->stream, dev_ring<W>(r), po, dig, cin,
+                           now, D, S, nrot, 0, sm, sc, wts, nrows, ostride);
+    else
+        hipLaunchKernelGGL((k_hoist_lincomb<W, 1, TL, false, RW>), dim3(ew_grid(tiles * r->n)), dim3(256), 0, r->stream, dev_ring<W>(r), po, dig, cin, now, D,
+                           S, nrot, 0, sm, sc, wts, nrows, ostride);
+}
+
+template <typename W>
+static int do_lincomb(const alch_automorph_set* a, const void* wts, size_t n_out, const void* in, void* out, size_t batch, const uint64_t* s_pre) {
+    alch_ring* r = a->ring;
+    const size_t ew = elem_words(r);
+    const size_t nblk = lincomb_blocks(n_out, LINCOMB_ROWS);
+    return hoist_walk<W>(a, in, batch, s_pre, [&](size_t done, size_t now, u32 GD, const W* pd, const W* cin, const HoistSet<W>& S, const Scal<W>& sm, bool scale) -> int {
+        for (size_t i = 0; i < nblk; ++i) {
+            const size_t g0 = i * LINCOMB_ROWS;
+            launch_hoist_lincomb<W>(r, reinterpret_cast<W*>(out) + (g0 * batch + done) * 2 * ew, pd, cin, now, GD, S, a->n_j, sm, scale,
+                                    reinterpret_cast<const W*>(wts) + g0 * a->n_j * ew, (u32)lincomb_block_rows(n_out, LINCOMB_ROWS, i), batch * 2 * ew);
+            HIP_TRY(hipGetLastError());
+        }
+        return ALCH_OK;
+    });
+}
+
+extern "C" int alch_ct_automorph_lincomb(const void* handle, const alch_buf* w_crt, size_t w_first, size_t n_out, const alch_buf* in, alch_buf* out,
+                                         size_t batch, const uint64_t* s_pre, unsigned flags) try {
+    const alch_automorph_set* a = reinterpret_cast<const alch_automorph_set*>(handle);
+    if (!a || !w_crt || !in || !out) return fail(ALCH_E_INVALID, "alch_ct_automorph_lincomb: null argument");
+    alch_ring* r = a->ring;
+    if (w_crt->ring != r || in->ring != r || out->ring != r)
+        return fail(ALCH_E_INVALID, "alch_ct_automorph_lincomb: the weights, the input and the output belong to the set's ring");
+    if (flags & ~(unsigned)(ALCH_POW_IN | ALCH_POW_OUT)) return fail(ALCH_E_INVALID, "alch_ct_automorph_lincomb: unknown flag");
+    if (flags)
+        return fail(ALCH_E_UNSUPPORTED, "alch_ct_automorph_lincomb: CRT basis in and out only (on the powerful basis sigma_j is not a permutation: transform first)");
+    if (batch == 0 || n_out == 0) return ALCH_OK;
+    const size_t R = a->n_j;
+    if (n_out > w_crt->n_elems / R || !range_ok(w_first, n_out * R, w_crt->n_elems))
+        return fail(ALCH_E_INVALID, "alch_ct_automorph_lincomb: w_crt holds n_out * n_j elements from w_first on");
+    if (!pairs_ok(batch, in->n_elems) || batch > out->n_elems / 2 / n_out)
+        return fail(ALCH_E_INVALID, "alch_ct_automorph_lincomb: in holds 2 * batch elements, out 2 * n_out * batch");
+    const size_t eb = elem_bytes(r);
+    const char* wp = reinterpret_cast<const char*>(w_crt->dptr) + w_first * eb;
+    if (bytes_overlap(out->dptr, 2 * n_out * batch * eb, in->dptr, 2 * batch * eb)) return fail(ALCH_E_INVALID, "alch_ct_automorph_lincomb: out must not alias the input");
+    if (bytes_overlap(out->dptr, 2 * n_out * batch * eb, wp, n_out * R * eb)) return fail(ALCH_E_INVALID, "alch_ct_automorph_lincomb: out must not alias the weights");
+    BIND(r);
+    return ALCH_BY_WORD(r, do_lincomb, a, wp, n_out, in->dptr, out->dptr, batch, s_pre);
 } catch (...) { return abi_catch(); }
 
 // ------------------------------------------------------------------------------------------------------

@@ -139,6 +139,16 @@ ALCH_HD u32 lazy_group(u32 q) {
     return kmax >= 4 ? (kmax - 2 > 8 ? 8u : kmax - 2) : 0u;
 }
 
+// Weighted sums of reduced values (kernel_lincomb.hpp): acc += y w for y < q and a CANONICAL weight w < q, neither in Montgomery form,
+// in groups of K = lazy_group(q) products under the bound above.  `carry` opens the next group: the running sum T comes back as
+// t = T R^-1 in [0, 2q) and is carried as t (R mod q) = T (mod q), below 2 q^2.  lincomb_close returns T mod q in [0, q): the last
+// reduction leaves T R^-1, and the product with R^2 mod q takes the factor out again (mont_mul_lazy takes any word on its left).
+ALCH_HD u64 lincomb_step(u64 acc, bool carry, u32 y, u32 w, u32 q, u32 qni, u32 r1) {
+    if (carry) acc = (u64)mont_red_lazy(acc, q, qni) * r1;
+    return acc + (u64)y * w;
+}
+ALCH_HD u32 lincomb_close(u64 acc, u32 q, u32 qni, u32 r2) { return csub(mont_mul_lazy(mont_red_lazy(acc, q, qni), r2, q, qni), q); }
+
 // The variant of dense_row a modulus allows: 2 below 2^32 / 6 (6 q < 2^32), 1 below 2^32 / sqrt(6) (6 q^2 < 2^64), else 0.
 ALCH_HD int dense_level(u64 q) { return q < 715827882ull ? 2 : q < 1753413056ull ? 1 : 0; }
 

@@ -178,3 +178,4 @@ foreign import ccall safe   "alch_ct_automorph"        c_ctAutomorph     :: Ptr 
 foreign import ccall safe   "alch_automorph_set_create" c_automorphSetCreate :: Ptr AlchRing -> Word32 -> Ptr Word32 -> CInt -> Ptr AlchBuf -> Ptr (Ptr ()) -> IO CInt
 foreign import ccall safe   "alch_automorph_set_free"  c_automorphSetFree :: Ptr () -> IO CInt
 foreign import ccall safe   "alch_ct_automorph_hoisted" c_ctAutomorphHoisted :: Ptr () -> Ptr AlchBuf -> Ptr AlchBuf -> CSize -> Ptr Word64 -> CUInt -> IO CInt
+foreign import ccall safe   "alch_ct_automorph_lincomb" c_ctAutomorphLincomb :: Ptr () -> Ptr AlchBuf -> CSize -> CSize -> Ptr AlchBuf -> Ptr AlchBuf -> CSize -> Ptr Word64 -> CUInt -> IO CInt

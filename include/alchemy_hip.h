@@ -255,7 +255,7 @@ int alch_buf_view(const alch_buf *parent, size_t first, size_t count, alch_buf *
  * Entry points between two rings whose limb counts differ (alch_ct_mod_switch(_deg), alch_buf_rescale_drop0 / _add0) cannot be
  * given overlapping ranges: a view keeps its parent's ring.  Those that accept one ring on both sides (alch_buf_embed / _twace /
  * _coeffs with equal indices, alch_ct_tunnel from a ring to itself, alch_ct_mul_full with operands and result on one ring,
- * alch_buf_automorph, alch_ct_automorph, alch_ct_automorph_hoisted) follow the rule without exception. */
+ * alch_buf_automorph, alch_ct_automorph, alch_ct_automorph_hoisted, alch_ct_automorph_lincomb) follow the rule without exception. */
 int alch_buf_elems(const alch_buf *buf, size_t *n_elems);
 /* Device address and size of the buffer (limb-major words, see above) for zero-copy hand-off to other device
  * code on the same GPU -- RCCL collectives that gather result batches, a caller's own kernels.
@@ -537,6 +537,25 @@ int alch_ct_automorph(const void *a, const alch_buf *in, alch_buf *out, size_t b
 int alch_automorph_set_create(alch_ring *ring, uint32_t n_j, const uint32_t *j, int gadget, const alch_buf *ks_crt, void **out);
 int alch_automorph_set_free(void *set);
 int alch_ct_automorph_hoisted(const void *set, const alch_buf *in, alch_buf *out, size_t batch, const uint64_t *s_pre, unsigned flags);
+
+/* ---- Weighted sums of hoisted rotations (added within 1.8; probe for the symbol) ------------------------------------------------------
+ * The diagonals of a slot-wise linear map: every rotation of the set times its own public CRT-basis element, summed, for n_out
+ * weightings (rows) of the same rotations at ONE gadget decomposition and without the rotations ever reaching memory.  With y_r[b]
+ * rotation r of ciphertext b as alch_ct_automorph_hoisted(set, in, ., batch, s_pre, 0) stores it, WORD FOR WORD
+ *       out[g batch + b].c_i[k] = sum_(r < n_j) w[w_first + g n_j + r][k] * y_r[b].c_i[k]   (mod q_limb),   i = 0, 1
+ * every stored word in [0, q): the words of that call followed by alch_buf_mul_public per (g, r) and alch_buf_add.  n_out = 1 with
+ * every weight crt(1) gives ALCH_AUTO_SUM's words; a row with crt(1) at r0 and zero elsewhere gives rotation r0.
+ *   w_crt   n_out * n_j CRT-basis elements of the set's ring from element w_first on, element w_first + g n_j + r the weight of
+ *           rotation r in row g: canonical residues, NOT in Montgomery form.  Read at call time in stream order, not copied.
+ *   in      batch linear ciphertexts with k = 0, CRT basis; s_pre as for alch_ct_automorph_hoisted.
+ *   out     n_out * batch ciphertexts, row g of ciphertext b at elements 2 (g batch + b) and 2 (g batch + b) + 1.
+ * Runs on the ring's stream in chunks of at most "scratch_mib", the rows in blocks of four per launch (a call with more rows redoes
+ * the inner products per block).  The input and the weights are not modified; out shares no byte with in or with the weight range.
+ * batch = 0 or n_out = 0: ALCH_OK, nothing queued.  Statuses, in this order: ALCH_E_INVALID (null argument; buffers of another ring;
+ * an unknown flag -- ALCH_AUTO_SUM is unknown here), ALCH_E_UNSUPPORTED (ALCH_POW_IN / ALCH_POW_OUT), ALCH_E_INVALID (a buffer shorter
+ * than its ciphertexts or weights; out overlapping in or the weights), device errors. */
+int alch_ct_automorph_lincomb(const void *set, const alch_buf *w_crt, size_t w_first, size_t n_out, const alch_buf *in, alch_buf *out, size_t batch,
+                              const uint64_t *s_pre, unsigned flags);
 
 /* ---- SymmSHE modSwitch on batches of linear ciphertexts (Eval.hs:130; the two modSwitch_ of PT2CT.hs:177 and :224-229) ----
  * The rings come from the handles; the smaller ring's moduli are the LAST limbs of the bigger ring's (Noise.hs:82-89).  The
